@@ -5,6 +5,14 @@ A step = one pass of the hot path over one batch already resident in HBM: kernel
 entropies, main.py:29-78), for every contig the rank owns.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5] [--launch graph|eager]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up the headline config, warms up, times its K steps and prints one JSON line
+(``value``, ``ms_per_step``: the wall-clock milliseconds one timed step took).  ``--dump-outputs
+DIR`` then writes what the last timed step computed as DIR/<name>.npy (float64; the inputs are
+seeded, so two builds can be compared output for output).  Everything else described below (the
+headline's per-kernel times, roofline and parity check, ``extra``, the CPU baselines, ``e2e``) is
+measured only with ``--full``.
 
 Headline (``value``), as BASELINE.json quotes its configs:
   * one GPU: config 2 (1 contig 29,903 bp, 100,000 reads x 150 bp, all-M CIGAR), one launch of
@@ -94,6 +102,7 @@ def amplicon_bytes(tiles, L: int) -> int:
 
 
 MALL_BYTES = 256 << 20  # MI355X Infinity Cache (MI355X_MICROARCH.md)
+DUMP_CAP_BYTES = 64 << 20  # --dump-outputs: all files of one run together stay under this
 
 
 def default_copies(cfg: str) -> int:
@@ -546,6 +555,48 @@ class Workload:
     def summaries(self) -> np.ndarray:
         return self.d_sum.download(np.float64, 4 * len(self.work)).reshape(-1, 4)
 
+    def outputs(self, slot: int = 0) -> dict:
+        """What a caller of the step receives, as the last step left it (--dump-outputs): every
+        contig's summary and amplicon rows where the step computes them, and the per-position
+        counts, coverage, percentages and entropies where it stores them, contigs concatenated
+        in the rank's order.  ``slot``: the context of ``pipelined`` the last step ran on (0: the
+        step's own buffers).  Integers are widened to float64 (exact).  Per-position arrays
+        beyond DUMP_CAP_BYTES in all are cut to the same seeded sample of each contig's
+        positions (``positions`` then holds the sampled indices, per contig)."""
+        out = {}
+        if self.summarise:
+            out["summary"] = self.summaries()
+        if self.d_tiles is not None:
+            out["amplicons"] = self.d_tiles[2].download(np.float64, 6 * len(self.tiles)).reshape(-1, 6)
+        if self.summary_only:
+            return out
+        k = self.k
+        per_pos = 8 * (k + 1 + (k if self.want_pc else 0) + 2)  # float64 bytes per position, all arrays
+        total = sum(w[1] for w in self.work)
+        budget = DUMP_CAP_BYTES - sum(a.nbytes for a in out.values())
+        keep = None
+        if per_pos * total > budget:
+            keep = budget // (per_pos + 8)  # (+ the sampled index itself)
+        parts = {n: [] for n in ("counts", "coverage", "percentages", "entropy", "secondary_entropy", "positions")}
+        for w, (t, L, _, _, o) in enumerate(self.work):
+            if slot:
+                o = self._pipe_out[slot][w]
+            idx = slice(None)
+            if keep is not None:
+                m = min(L, keep * L // total)
+                idx = np.sort(np.random.default_rng(20240 + t).choice(L, m, replace=False))
+                parts["positions"].append(idx.astype(np.float64))
+            parts["counts"].append(o["counts"].download(np.int32, k * L).reshape(k, L)[:, idx].astype(np.float64))
+            parts["coverage"].append(o["cov"].download(np.int32, L)[idx].astype(np.float64))
+            if o["pc"] is not None:
+                parts["percentages"].append(o["pc"].download(np.float64, k * L).reshape(k, L)[:, idx])
+            parts["entropy"].append(o["ent"].download(np.float64, L)[idx])
+            parts["secondary_entropy"].append(o["sec"].download(np.float64, L)[idx])
+        for n, p in parts.items():
+            if p:
+                out[n] = np.concatenate(p, axis=-1)
+        return out
+
     def bytes_dominant(self, dom: str) -> int:
         return sum(kernel_bytes(dom, read_bytes(b, self.mbq, self.rs.l_seq[self.rs.tid == t]), L, self.k,
                                 self.want_pc) for t, L, b, _, _ in self.work)
@@ -602,6 +653,16 @@ def compact(x, digits: int = 4):
     return x
 
 
+def dump_outputs(dirname: str, arrays: dict, rank: int, world: int) -> None:
+    """--dump-outputs: one DIR/<name>.npy per array of Workload.outputs (float64); with several
+    ranks every rank writes its own share as <name>_rank<r>.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_CAP_BYTES
+    for name, a in arrays.items():
+        assert a.dtype == np.float64
+        np.save(os.path.join(dirname, name + (f"_rank{rank}" if world > 1 else "") + ".npy"), a)
+
+
 def max_over_ranks(group, seconds: float) -> float:
     if group is None:
         return seconds
@@ -639,9 +700,10 @@ def gather_rows_summaries(ctx, group, wl, rank: int, world: int) -> float:
 
 
 def run_config(cfg: str, ctx, group, args, rank: int, world: int, steps: int, warmup: int,
-               launch: str, summarise: bool, summary_only: bool = False) -> dict:
+               launch: str, summarise: bool, summary_only: bool = False, dump: str | None = None) -> dict:
     """Time K steps of one config (the bench contract: W warmup, barrier + sync on both sides,
-    max over ranks) and describe them."""
+    max over ranks) and, with --full, describe them: per-kernel times, the roofline, the parity
+    check.  ``dump``: the directory the last timed step's outputs are written to."""
     from basecount_amd import device as D
 
     copies = args.rotate if args.rotate > 0 else default_copies(cfg)
@@ -747,6 +809,38 @@ def run_config(cfg: str, ctx, group, args, rank: int, world: int, steps: int, wa
     del graph
     if trial is not None:
         del graphs
+    if dump:
+        # the outputs of the last timed step, before anything else runs: with n steps in flight
+        # step K-1 ran on context (K-1) mod n
+        dump_outputs(dump, wl.outputs((steps - 1) % in_flight if pipe else 0), rank, world)
+    res = {
+        "workload": WORKLOADS[cfg],
+        "value": wl.total_positions * steps / elapsed,
+        "unit": "positions/s",
+        "ms_per_step": elapsed / steps * 1e3,
+        "steps": steps, "warmup": warmup,
+        "scaling": "strong" if wl.per_contig else "weak",
+        "gbases_piled_per_s": (1 if wl.per_contig else world) * wl.events() * steps / elapsed / 1e9,
+        "device_us_per_step": dev_step * 1e6,
+        "steps_in_flight": in_flight,
+        "launch_trial_us": trial,
+        "reads_per_rank": int(sum(int(w[2]["pos"].size) for w in wl.work)),
+        "positions_per_rank": int(sum(w[1] for w in wl.work)),
+        "contigs_per_rank": len(wl.work),
+        "streams": len(wl.ctxs),
+        "upload_ms": wl.upload_s * 1e3,
+        "batch_copies": wl.copies,
+    }
+    if per_rank is not None:
+        res["per_rank_device_us"] = per_rank
+    if gather is not None:
+        res["gather_bytes"] = int(gather[0].sum())
+    if not args.full:  # a plain run: the timed steps alone, nothing measured or checked beside them
+        for sd in sides:
+            sd.sync()
+            sd.close()
+        res["_wl"] = wl
+        return res
 
     # which kernels a step launches (library timing facility, per-launch event pairs)
     ctx.timing(True)
@@ -849,33 +943,15 @@ def run_config(cfg: str, ctx, group, args, rank: int, world: int, steps: int, wa
         if (pm and pm.get("mbq", 0) == args.mbq and pm.get("kernel", "pileup") == dom
                 and pm.get("lib_sha16") == lib_sha16() and pm.get("copies", 1) == copies):
             traffic = pm.get("hbm_bytes_per_launch")
-    res = {
-        "workload": WORKLOADS[cfg],
-        "value": wl.total_positions * steps / elapsed,
-        "unit": "positions/s",
-        "ms_per_step": elapsed / steps * 1e3,
-        "steps": steps, "warmup": warmup,
-        "scaling": "strong" if wl.per_contig else "weak",
-        "gbases_piled_per_s": (1 if wl.per_contig else world) * wl.events() * steps / elapsed / 1e9,
-        "device_us_per_step": dev_step * 1e6,
+    res.update({
         "kernel_us": {n: v * 1e6 for n, v in kern_s.items()},
-        "steps_in_flight": in_flight,
-        "launch_trial_us": trial,
-        "reads_per_rank": int(sum(int(w[2]["pos"].size) for w in wl.work)),
-        "positions_per_rank": int(sum(w[1] for w in wl.work)),
-        "contigs_per_rank": len(wl.work),
-        "streams": len(wl.ctxs),
-        "upload_ms": wl.upload_s * 1e3,
-        "batch_copies": wl.copies,
         "parity_vs_oracle": parity,
         "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "kernel": dom,
                      "basis": ("device_us_per_step" if len(wl.ctxs) > 1 else "kernel_us"),
                      "algorithmic_bytes": kbytes},
-    }
+    })
     res.update(extra_us)
-    if per_rank is not None:
-        res["per_rank_device_us"] = per_rank
     if wl.tiles is not None and "amplicons" in kern_s:
         ab = amplicon_bytes(wl.tiles, wl.work[0][1])
         res["amplicon_roofline"] = {"achieved": ab / kern_s["amplicons"] / 1e9,
@@ -883,17 +959,20 @@ def run_config(cfg: str, ctx, group, args, rank: int, world: int, steps: int, wa
                                     "algorithmic_bytes": ab, "windows": len(wl.tiles)}
     if gather_us is not None:
         res["gather_us"] = gather_us
-        res["gather_bytes"] = int(gather[0].sum())
     res["_wl"] = wl
     return res
 
 
-def run_c5(ctx, group, args, rank: int, world: int, steps: int, warmup: int, launch: str) -> dict:
+def run_c5(ctx, group, args, rank: int, world: int, steps: int, warmup: int, launch: str,
+           dump: str | None = None) -> dict:
     """C5 as --summarise runs it: the summary-only call (read-parallel, no
     per-position output; main.py:469-499 prints six numbers per contig) is the step; the storing sweep (every
     count, coverage and entropy written, as the library API, rows and --summarise-with-bed need
     them) is timed after it on the same contigs and reported beside it as `storing`."""
-    r = run_config("c5", ctx, group, args, rank, world, steps, warmup, launch, summarise=True, summary_only=True)
+    r = run_config("c5", ctx, group, args, rank, world, steps, warmup, launch, summarise=True, summary_only=True,
+                   dump=dump)
+    if not args.full:  # the step alone
+        return r
     r.pop("_wl").free()
     s = run_config("c5", ctx, group, args, rank, world, steps, warmup, launch, summarise=True, summary_only=False)
     wl = s.pop("_wl")
@@ -1182,6 +1261,14 @@ def main():
                     help="headline workload (default: c2 on one GPU; c5, BASELINE's multi-GPU config, sharded "
                          "over the ranks with the RCCL gather, on several)")
     ap.add_argument("--mbq", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline's timed steps: its per-kernel times, roofline and parity check, "
+                         "the other configs (extra), the CPU baselines and the CLI end to end (the --no-* "
+                         "switches below trim these); without it the run sets up, warms up, times the steps "
+                         "and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (the headline config's "
+                         "outputs, float64) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget", type=float, default=10.0)
     ap.add_argument("--no-extras", action="store_true", help="headline config only")
@@ -1263,20 +1350,20 @@ def main():
             group.fallback = f"rccl failed: {e}"
 
     if args.config == "c5":
-        head = run_c5(ctx, group, args, rank, world, args.steps, args.warmup, args.launch)
+        head = run_c5(ctx, group, args, rank, world, args.steps, args.warmup, args.launch, args.dump_outputs)
     else:
         head = run_config(args.config, ctx, group, args, rank, world, args.steps, args.warmup, args.launch,
-                          summarise=args.config == "c4")
+                          summarise=args.config == "c4", dump=args.dump_outputs)
     wl = head.pop("_wl")
     # ---- gather of the per-contig summaries to rank 0 (the output step, after the timed region)
     gather_ms = None
-    if group is not None and args.config not in ("c4", "c5"):
+    if args.full and group is not None and args.config not in ("c4", "c5"):
         gather_ms = gather_rows_summaries(ctx, group, wl, rank, world)
     wl.free()
     del wl
 
     extra = {}
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         # one GPU: the other single-GPU configs and C5; several: C5 is the headline (strong scaling,
         # sharded + gathered) and C2 weak scaling (each rank its own contig) rides along
         todo = (["c3", "c4", "c5"] if world == 1 else ["c2", "c5"])
@@ -1317,7 +1404,7 @@ def main():
             extra["c3_split"] = run_split(ctx, group, min(args.steps, 100), min(args.warmup, 10))
 
     cpu = cpu_all = e2e_res = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         from basecount_amd import synth
 
         if not args.no_cpu_baseline and args.config == "c2":
@@ -1371,9 +1458,10 @@ def main():
                        "comm_fallback": getattr(group, "fallback", None),
                        "tile_index": args.tile_index, "read_runs": args.read_runs,
                        "batch_copies": head["batch_copies"], "build": build, "lib_sha16": lib_sha16()},
-            "roofline": head["roofline"],
-            "cpu_baseline": cpu,
         }
+        if args.full:
+            line["roofline"] = head["roofline"]
+            line["cpu_baseline"] = cpu
         for key in ("steps_in_flight", "serial_us_per_step", "serial_device_us_per_step", "device_us_per_step",
                     "kernel_us", "launch_trial_us", "gbases_piled_per_s", "upload_ms", "gather_us", "gather_bytes",
                     "per_rank_device_us", "parity_vs_oracle"):
@@ -1396,7 +1484,7 @@ def main():
             if cfg in line["extra"] and "e2e" in line["extra"][cfg]:
                 line.setdefault("e2e_extra", {})[cfg] = line["extra"][cfg].pop("e2e")
         print(json.dumps(compact(line), separators=(",", ":")), flush=True)
-    ok = head["parity_vs_oracle"] and all(r["parity_vs_oracle"] for r in extra.values())
+    ok = head.get("parity_vs_oracle", True) and all(r["parity_vs_oracle"] for r in extra.values())
     if group is not None:
         group.close()
     if not ok:

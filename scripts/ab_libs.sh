@@ -10,7 +10,7 @@ cp "$LIB" /tmp/lib_orig.so
 for rep in $(seq "$REPS"); do
   for v in $LIBS; do
     cp "$v" "$LIB"
-    out=$(timeout -k 10 300 python bench.py --config "$CONFIG" --no-cpu-baseline --no-extras --no-e2e --steps "$STEPS" --warmup 20 ${BENCH_ARGS}) || { echo "FAILED $v"; cp /tmp/lib_orig.so "$LIB"; exit 1; }
+    out=$(timeout -k 10 300 python bench.py --full --config "$CONFIG" --no-cpu-baseline --no-extras --no-e2e --steps "$STEPS" --warmup 20 ${BENCH_ARGS}) || { echo "FAILED $v"; cp /tmp/lib_orig.so "$LIB"; exit 1; }
     echo "$out" | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$(basename $v)', '$CONFIG', round(d['ms_per_step']*1e3,2), 'us/step', {k: round(x,2) for k,x in d['kernel_us'].items()}, 'parity', d['parity_vs_oracle'])"
   done
 done

@@ -15,7 +15,7 @@ for c in ${CFGS:-c2 c3 c3q20 c4 c5}; do
   [ "$c" = c5 ] && steps=5 && extra="--streams 1"  # c5: launches serialized, so their durations add up
   [ "$c" = c3q20 ] && cfg=c3 && extra="--mbq 20"   # C3 with the quality test (QUAL bytes read)
   timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_$c -o run -- \
-    python bench.py --config $cfg --no-cpu-baseline --no-extras --no-e2e --lean --launch eager --steps $steps --warmup 2 $extra \
+    python bench.py --full --config $cfg --no-cpu-baseline --no-extras --no-e2e --lean --launch eager --steps $steps --warmup 2 $extra \
     > gpurun_out/prof_$c.log 2>&1
   rc=$?; echo "trace $c rc=$rc"; fatal $rc && exit $rc
   pargs="--config $cfg"; [ "$c" = c3q20 ] && pargs="$pargs --mbq 20"; [ "$c" = c5 ] && pargs="$pargs --steps 5 --streams 1"

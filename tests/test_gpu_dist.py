@@ -123,7 +123,7 @@ def test_bench_gpus_2_rehearsal():
     env = dict(os.environ, BASECOUNT_DIST_BACKEND="gloo")
     for v in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(v, None)
-    p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "5",
+    p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--full", "--steps", "5",
                         "--warmup", "2"], env=env, capture_output=True, timeout=600, cwd=REPO)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     lines = [ln for ln in p.stdout.decode().splitlines() if ln.startswith("{")]

@@ -33,29 +33,19 @@ def test_oracle_bcount_matches_reference_vectors(golden):
             assert out.tolist() == v["expected"], name
 
 
-def test_oracle_matches_compiled_reference_on_random_reads():
+def test_oracle_matches_compiled_reference_on_random_reads(golden):
+    """20 seeded random read sets with what the reference's compiled count.bcount returned for
+    them (tests/golden/make_random_vectors.py); where oracle/_ref is built, it is run again."""
+    with gzip.open(os.path.join(golden, "bcount", "random_vectors.json.gz")) as fh:
+        vec = json.load(fh)
+    assert len(vec) == 20
     ref = O.ref_bcount()
-    if ref is None:
-        pytest.skip("oracle/_ref not built (reference sources absent)")
-    rng = np.random.default_rng(5)
-    for trial in range(20):
-        L = int(rng.integers(50, 400))
-        reads, quals, starts, ctuples = [], [], [], []
-        for _ in range(int(rng.integers(0, 60))):
-            ops = [(0, int(rng.integers(1, 20)))]
-            for _ in range(int(rng.integers(0, 4))):
-                ops.append((int(rng.choice([0, 1, 2, 3, 6, 7, 8, 9])), int(rng.integers(1, 6))))
-            ops.append((0, int(rng.integers(1, 20))))
-            span = sum(n for o, n in ops if o in (0, 2, 3, 7, 8))
-            q = sum(n for o, n in ops if o in (0, 1, 7, 8))
-            if span >= L:
-                continue
-            reads.append("".join(rng.choice(list("ACGTN=RYacgt"), q)))
-            quals.append(rng.integers(0, 45, q).tolist())
-            starts.append(int(rng.integers(0, L - span)))
-            ctuples.append(ops)
-        mbq = int(rng.choice([0, 10, 30]))
-        exp = ref(L, mbq, reads, quals, starts, ctuples)
+    for trial, v in enumerate(vec):
+        L, mbq, reads, quals, starts = v["ref_len"], v["mbq"], v["reads"], v["qualities"], v["starts"]
+        ctuples = [[tuple(t) for t in c] for c in v["ctuples"]]
+        exp = v["expected"]
+        if ref is not None:
+            assert ref(L, mbq, reads, quals, starts, ctuples) == exp, trial
         out, (br, _) = O.bcount(L, mbq, pack(reads, quals, starts, ctuples))
         assert br == -1 and out.tolist() == exp, trial
 
