@@ -12,6 +12,7 @@
 
 #include "bc_internal.h"
 #include "bc_log2.h"
+#include "bc_stats.h"
 
 namespace bc {
 namespace {
@@ -530,32 +531,10 @@ __global__ __launch_bounds__(256) void k_stats_oct(int32_t* __restrict__ hist, i
     uint32_t c[K];
 #pragma unroll
     for (int i = 0; i < K; ++i) c[i] = (uint32_t)__shfl((int)cj, i, 8);
-    int64_t cov = 0;
-    int am = 0;
-    uint32_t mx = c[0];
-#pragma unroll
-    for (int i = 0; i < K; ++i) {
-        cov += c[i];
-        if (c[i] > mx) mx = c[i], am = i;  // np.argmax: first maximum
-    }
-    const bool one = cov != 0 && cov == (int64_t)mx;  // one class only: the terms are exact constants
-    const int64_t cov2 = cov - (int64_t)mx;
-    double t = 0.0, u = 0.0;
-    if (col && cov != 0) {
-        if (one) {
-            if (pc) pc[(int64_t)j * L + P] = j == am ? 100.0 : 0.0;
-        } else {
-            const double pj = (double)cj / (double)cov;
-            if (pc) pc[(int64_t)j * L + P] = 100.0 * pj;
-            if (cj != 0) t = -(pj * glibc_log2_t(pj, tab));
-            if (sec && cov2 != 0 && j != am && cj != 0) {
-                const double q = (double)cj / (double)cov2;
-                u = -(q * glibc_log2_t(q, tab));
-            }
-        }
-    } else if (col && pc) {
-        pc[(int64_t)j * L + P] = -1.0;
-    }
+    double pct, t, u;
+    const OctPos o = oct_pos<K>(c);
+    oct_terms(o, cj, j, col, sec != nullptr, tab, pct, t, u);
+    if (col && pc) pc[(int64_t)j * L + P] = pct;
     double ts[K], us[K];
 #pragma unroll
     for (int i = 0; i < K; ++i) {
@@ -563,24 +542,9 @@ __global__ __launch_bounds__(256) void k_stats_oct(int32_t* __restrict__ hist, i
         us[i] = __shfl(u, i, 8);
     }
     if (!in || j != 0) return;
-    if (cov_out) cov_out[P] = (int32_t)cov;
-    double h = 1.0, h2 = 1.0;
-    if (one) {
-        h = 0.0;
-    } else if (cov != 0) {
-        double s1 = 0.0;
-#pragma unroll
-        for (int i = 0; i < K; ++i)
-            if (c[i] != 0) s1 = s1 + ts[i];
-        h = nf * s1;
-        if (cov2 != 0) {
-            double s2 = 0.0;
-#pragma unroll
-            for (int i = 0; i < K; ++i)
-                if (i != am && c[i] != 0) s2 = s2 + us[i];
-            h2 = nf2 * s2;
-        }
-    }
+    if (cov_out) cov_out[P] = (int32_t)o.cov;
+    double h, h2;
+    oct_sums<K, K>(c, o, ts, us, nf, nf2, h, h2);
     if (ent) ent[P] = h;
     if (sec) sec[P] = h2;
 }

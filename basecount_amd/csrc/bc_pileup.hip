@@ -10,9 +10,10 @@
 // ONE 32-bit word (a funnel shift of the BC_SEQ_EVENT sequence per CIGAR run, deletions as class
 // 1100) and counts all 8 positions x 6 columns with SWAR nibble counters: ~30 VALU per 8 bases.
 // No atomics and no histogram memset: the 8 read slots are reduced with DPP, the S waves of a
-// group through LDS, the tile's counts are written once with coalesced stores (count.cpp's
-// baseCounts), and the per-position statistics of main.py:29-53 are computed in the same launch
-// (kernel 2 fused).  Reads with more than 8 CIGAR ops / 4 runs take a per-position walk.
+// group through LDS atomics, and the per-position statistics of main.py:29-53 are computed in the
+// same launch (kernel 2 fused: tile_tail, every wave of the group finishing and storing its own
+// positions, counts included: count.cpp's baseCounts).  Reads with more than 8 CIGAR ops / 4 runs
+// take a per-position walk.
 //
 // Positions >= L (the last, partial tile and "edge" tiles past the reference end, up to the
 // furthest read end) do not count: a counted event there is the reference's std::out_of_range
@@ -22,8 +23,94 @@
 namespace bc {
 namespace {
 
+// LDS seen as LDS: the tail's reads must be ds_read, not flat loads of a generic pointer.
+typedef __attribute__((address_space(3))) const uint32_t lds_u32;
+typedef __attribute__((address_space(3))) const double lds_f64;
+struct LdsLog2Tab {  // log2d::kTab copied to LDS, indexable as tab[i][j] (glibc_log2_t)
+    lds_f64* p;
+    __device__ __forceinline__ lds_f64* operator[](int i) const { return p + 4 * i; }
+};
+
+// The value of the lane N places up in the same 16-lane row (DPP row_shl: no LDS traffic).  Run
+// it with every lane active: an inactive source lane reads as 0.
+template <int N>
+__device__ __forceinline__ double row_up(double v) {
+    if (N == 0) return v;
+    const uint64_t b = __builtin_bit_cast(uint64_t, v);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)b, 0x100 + N, 0xF, 0xF, true);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(b >> 32), 0x100 + N, 0xF, 0xF, true);
+    return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
+}
+
+// Column j's percentage and terms (oct_terms) with the log2 table in LDS.  Kept out of line:
+// inlined, the log2 constants are hoisted out of the tile loop into registers the read walk
+// needs.  It touches no global memory, so the call's entry and return wait for nothing.
+struct ColTerms {
+    double pct, t, u;
+};
+__device__ __attribute__((noinline)) ColTerms col_terms(OctPos o, uint32_t cj, int j, bool col, lds_f64* tab) {
+    ColTerms r;
+    oct_terms(o, cj, j, col, true, LdsLog2Tab{tab}, r.pct, r.t, r.u);
+    return r;
+}
+
+// The first lane of each position adds its NS columns' terms (oct_sums).
+template <int K, int NS>
+__device__ __forceinline__ void tail_sums(const uint32_t (&c)[K], const OctPos& o, double t, double u, double nf,
+                                          double nf2, double& h, double& h2) {
+    double ts[K], us[K];
+#pragma unroll
+    for (int i = 0; i < K; ++i) ts[i] = us[i] = 0.0;
+    ts[0] = t, us[0] = u;
+    ts[1] = row_up<1>(t), us[1] = row_up<1>(u);
+    ts[2] = row_up<2>(t), us[2] = row_up<2>(u);
+    ts[3] = row_up<3>(t), us[3] = row_up<3>(u);
+    if (NS > 4) ts[4] = row_up<4>(t), us[4] = row_up<4>(u);
+    if (NS > 5) ts[5] = row_up<5>(t), us[5] = row_up<5>(u);
+    oct_sums<K, NS>(c, o, ts, us, nf, nf2, h, h2);
+}
+
+// Fused kernel 2: the statistics of a tile from its reduced counts f[K][kTile] in LDS, eight
+// lanes per position (bc_stats.h: lane j < K owns column j; the position's first lane adds the
+// terms).  A wave finishes 8 positions per pass: the tile's eight 8-position groups `first`,
+// `first + step`, ... are this wave's.  Nothing is read from global memory (the log2 table is in
+// LDS), and a pass stores its counts, percentages, coverage and entropies last: the stores wait
+// for nothing, and nothing but the wave's next pass or tile waits for them.
+template <int K, typename ARGS>
+__device__ __forceinline__ void tile_tail(const ARGS& A, lds_u32* f, lds_f64* tab, int first, int step, int64_t t0,
+                                          int64_t L, int lane) {
+    // (the tail's lane-derived indices and addresses are computed here, not hoisted out of the
+    // tile loop and kept in registers through the read walk)
+    asm volatile("" : "+v"(lane));
+    const int j = lane & 7;
+    for (int q = first; q < kTile / 8; q += step) {
+        const int p = 8 * q + (lane >> 3);
+        const int64_t P = t0 + p;
+        const bool col = j < K && P < L;
+        uint32_t c[K];
+#pragma unroll
+        for (int i = 0; i < K; ++i) c[i] = f[i * kTile + p];
+        const uint32_t cj = f[(j < K ? j : 0) * kTile + p];
+        const OctPos o = oct_pos<K>(c);
+        const ColTerms r = col_terms(o, cj, j, col, tab);
+        // batches without deletions or N: those columns' terms are zero in every lane (uniform)
+        double h, h2;
+        if (__any(col && j >= 4 && cj != 0)) tail_sums<K, K>(c, o, r.t, r.u, A.nf, A.nf2, h, h2);
+        else tail_sums<K, 4>(c, o, r.t, r.u, A.nf, A.nf2, h, h2);
+        if (col) {
+            A.counts[(int64_t)j * L + P] = (int32_t)cj;
+            if (A.pc) A.pc[(int64_t)j * L + P] = r.pct;
+        }
+        if (j == 0 && P < L) {
+            A.cov[P] = (int32_t)o.cov;
+            A.ent[P] = h;
+            A.sec[P] = h2;
+        }
+    }
+}
+
 template <bool QUAL, int K, bool STATS, typename IT>
-__global__ __launch_bounds__(512, 4) void k_pileup(PileArgs A) {
+__global__ __launch_bounds__(512, 4) void k_pileup(TileArgs A) {
     extern __shared__ __attribute__((aligned(16))) unsigned char dyn[];
     __shared__ IT rng[8][2];  // per group: the tile's read range
     if (BC_ABL(A) & 64) return;
@@ -37,14 +124,17 @@ __global__ __launch_bounds__(512, 4) void k_pileup(PileArgs A) {
     uint4* rec_all = (uint4*)dyn;
     uint8_t* stage_all = dyn + (size_t)nw * kRecBytes;
     uint32_t(*fin)[6][kTile] = (uint32_t(*)[6][kTile])(stage_all + (size_t)nw * kStageRegion);
-    // aliases of the stage regions, live only after the walk (see pileup_lds_bytes)
-    double* terms_g = (double*)(stage_all + (size_t)(g * S) * kStageRegion);
+    double2* tab = (double2*)((uint8_t*)fin + (size_t)groups * kFinBytes);  // log2d::kTab for the tail
     // IT: the index type of reads, tiles and positions (int32_t when they fit: scalar math)
     const IT n_tiles = (IT)A.n_tiles;
     const IT nblk_tiles = (n_tiles + groups - 1) / groups;
     const IT L = (IT)A.L;
     const int s8 = lane & 7;
     const bool qual_vec = ((uintptr_t)A.qual & 15u) == 0;
+    if (STATS && S == 1) {  // no barrier per tile: the table is copied once
+        if (threadIdx.x < 128) tab[threadIdx.x] = ((const double2*)log2d::kTab)[threadIdx.x];
+        __syncthreads();
+    }
 
     // XCD-aware: workgroups are dispatched round-robin over the 8 XCDs; give each XCD a
     // contiguous run of tiles so neighbouring tiles (which share ~2/3 of their reads) hit the
@@ -61,6 +151,10 @@ __global__ __launch_bounds__(512, 4) void k_pileup(PileArgs A) {
         // the tile's reads [lo, hi): searched by the group's first wave (the S waves would all
         // find the same range), handed to the others through LDS
         IT lo = 0, hi = 0;
+        // the log2 table's way to LDS shares the range's memory round trip (S > 1: written again
+        // for every tile, which costs one L2 hit and keeps four registers out of the tile loop)
+        double2 tabv = {0.0, 0.0};
+        if (STATS && S > 1 && threadIdx.x < 128) tabv = ((const double2*)log2d::kTab)[threadIdx.x];
         if (ws == 0 && t < n_tiles && !(BC_ABL(A) & 2)) {
 #ifdef BC_PHASE_TRACE
             if (A.trace) {  // diagnostic: latency of one dependent global load from here
@@ -93,6 +187,7 @@ __global__ __launch_bounds__(512, 4) void k_pileup(PileArgs A) {
 #pragma unroll
                 for (int c = 0; c < K; ++c) fin[g][c][lane] = 0u;
             }
+            if (STATS && threadIdx.x < 128) tab[threadIdx.x] = tabv;
             __syncthreads();
             trace_stamp(A, 1);
             lo = rng[g][0];
@@ -143,77 +238,52 @@ __global__ __launch_bounds__(512, 4) void k_pileup(PileArgs A) {
             }
         }
         // ---- reduce the S waves of the group: LDS atomics into fin (zeroed before the range
-        // barrier), so every wave reads the totals after one barrier
+        // barrier), so every wave reads the totals after one barrier.  S == 1: the wave's own
+        // counts, handed to its own tail through LDS (no other wave touches fin[g]).
+        const bool more = bt + G < nblk_tiles;  // (uniform over the block) another tile follows
         if (S > 1) {
 #pragma unroll
             for (int c = 0; c < K; ++c) atomicAdd(&fin[g][c][lane], cnt[c]);
             __syncthreads();
             trace_stamp(A, 4);
-            if (ws == 0) {
+            if (!STATS && ws == 0) {
 #pragma unroll
                 for (int c = 0; c < K; ++c) cnt[c] = fin[g][c][lane];
             }
+        } else if (STATS) {
+#pragma unroll
+            for (int c = 0; c < K; ++c) fin[g][c][lane] = cnt[c];
+            __builtin_amdgcn_wave_barrier();
         }
         const bool own = t < n_tiles && t0 < L && !(BC_ABL(A) & 16);  // tile holds real positions
-        if (ws == 0) {
+        if (!STATS) {
+            if (ws == 0 && own && P < L) {
 #pragma unroll
-            for (int c = 0; c < K; ++c) {
-                if (own && P < L) {
+                for (int c = 0; c < K; ++c) {
                     int32_t* dst = A.counts + (int64_t)c * L + P;
                     if (A.accumulate) cnt[c] += (uint32_t)*dst;
                     *dst = (int32_t)cnt[c];
                 }
-                if (S == 1 || A.accumulate) fin[g][c][lane] = cnt[c];
             }
+        } else {
+            trace_stamp(A, 5);
+            // ---- fused kernel 2: every wave finishes its share of the tile's positions and
+            // stores them, counts included
+            if (own && !(BC_ABL(A) & 8))
+                tile_tail<K>(A, (lds_u32*)&fin[g][0][0], (lds_f64*)tab, ws, S, (int64_t)t0, (int64_t)L, lane);
+            trace_stamp(A, 6);
         }
-        if (!STATS || (BC_ABL(A) & 8)) {
-            if (S > 1) __syncthreads();
-            continue;
-        }
-        if (S == 1 || A.accumulate) __syncthreads();  // (uniform) fin written by wave 0 above
-        trace_stamp(A, 5);
-        // ---- fused kernel 2: per-lane fp64 terms, then ordered sums per position
-        if (own) tile_terms<K>(A, &fin[g][0][0], terms_g, t0, ws * 64 + lane, S * 64);
-        __syncthreads();
-        trace_stamp(A, 6);
-        if (own && ws == 0 && P < L) {
-            int64_t cov = 0;
-            uint32_t mx = 0;
-#pragma unroll
-            for (int j = 0; j < K; ++j) {
-                cov += cnt[j];
-                mx = cnt[j] > mx ? cnt[j] : mx;
-            }
-            A.cov[P] = (int32_t)cov;
-            double h = 1.0, h2 = 1.0;
-            if (cov != 0) {
-                double s = 0.0;
-#pragma unroll
-                for (int j = 0; j < K; ++j)
-                    if (cnt[j] != 0) s = s + terms_g[j * kTile + lane];
-                h = A.nf * s;
-                if (cov - (int64_t)mx != 0) {
-                    double s2 = 0.0;
-#pragma unroll
-                    for (int j = 0; j < K; ++j) {
-                        const double tj = terms_g[(K + j) * kTile + lane];
-                        if (tj != 0.0) s2 = s2 + tj;
-                    }
-                    h2 = A.nf2 * s2;
-                }
-            }
-            A.ent[P] = h;
-            A.sec[P] = h2;
-        }
-        __syncthreads();
+        // fin and rng are written again for the block's next tile: not before every wave has read
+        // them.  The last tile (every tile of a one-round grid) ends without a barrier.
+        if (S > 1 && more) __syncthreads();
         trace_stamp(A, 7);
     }
 }
 
 // ---- sparse batches (at most ~48 reads per tile): one wave per tile, tiles swept in order ----
 
-// Kernel 2 for one position from its counts (bc_stats.h: the same arithmetic as tile_terms + the
-// ordered sums of k_pileup), written by the position's lane.
+// Kernel 2 for one position from its counts (bc_stats.h: the bits of k_pileup's tail), written
+// by the position's lane.
 template <int K>
 __device__ __forceinline__ double pos_stats(const PileArgs& A, const uint32_t* c, int64_t P) {
     return position_stats<K>(c, A.L, P, A.nf, A.nf2, A.cov, A.pc, A.ent, A.sec);
@@ -556,6 +626,7 @@ hipError_t launch_pileup_tiles(hipStream_t s, const bc_reads& r, int64_t L, int6
     blocks = (blocks + 7) / 8 * 8;  // a multiple of the XCD count (see the kernel's tile mapping)
     const dim3 grid((unsigned)blocks), block(64 * nw);
     const size_t lds = pileup_lds_bytes(nw, groups);
+    if (stats && accumulate) return hipErrorInvalidValue;  // no caller: the fused tail only stores
     // diagnostic only: BC_TRACE=<file> dumps the per-wave phase stamps of the 20th launch
     static unsigned long long* tbuf = nullptr;
     static int tcalls = 0;
@@ -571,6 +642,7 @@ hipError_t launch_pileup_tiles(hipStream_t s, const bc_reads& r, int64_t L, int6
     }
     // 32-bit reads, tiles and positions when they fit
     const bool i32 = A.n < (int64_t)0x7FFFFF00 && A.n_tiles * kTile + A.max_span + 2 * kTile < (int64_t)0x7FFFFF00;
+    const TileArgs T = A;  // k_pileup takes the walk's fields only
     // > 64 KiB of dynamic LDS must be allowed per kernel (160 KiB per CU on gfx950)
 #define BC_PILE(Q, KK, ST)                                                                                   \
     do {                                                                                                     \
@@ -582,8 +654,8 @@ hipError_t launch_pileup_tiles(hipStream_t s, const bc_reads& r, int64_t L, int6
                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024);        \
             attr_set = true;                                                                                 \
         }                                                                                                    \
-        if (i32) hipLaunchKernelGGL((k_pileup<Q, KK, ST, int32_t>), grid, block, lds, s, A);                 \
-        else hipLaunchKernelGGL((k_pileup<Q, KK, ST, int64_t>), grid, block, lds, s, A);                     \
+        if (i32) hipLaunchKernelGGL((k_pileup<Q, KK, ST, int32_t>), grid, block, lds, s, T);                 \
+        else hipLaunchKernelGGL((k_pileup<Q, KK, ST, int64_t>), grid, block, lds, s, T);                     \
         if (A.trace && ++tcalls == 20) {                                                                     \
             (void)hipStreamSynchronize(s);                                                                   \
             if (FILE* f = std::fopen(tpath, "wb")) {                                                         \

@@ -22,7 +22,10 @@ constexpr int kJunk = 60;
 constexpr int kBatch = 8;   // reads whose sequence loads are in flight together
 constexpr int kStageRegion = kStage + 32;  // + one 16-byte pad before and after
 
-struct PileArgs {
+// What the position-tiled walk (process_chunk and below) and k_pileup read.  Kept apart from the
+// sweep / summary fields of PileArgs: a kernel argument block is loaded into scalar registers, and
+// k_pileup has none to spare.
+struct TileArgs {
     const int32_t* pos;
     const uint32_t* cig_beg;
     const uint32_t* cig_n;
@@ -48,6 +51,13 @@ struct PileArgs {
     int64_t n_trange;
     int64_t seq_words;   // readable 32-bit words of seq (bc_seq_event_bytes / 4)
     int64_t qual_bytes;
+    int ablate;  // diagnostic only (BC_ABLATE): 1 no reads, 2 no search, 4 no walk, 8 no stats
+                 // math, 16 no stores, 32 no sequence staging
+    unsigned long long* trace;  // diagnostic only (BC_TRACE): per-wave phase stamps, else null
+};
+
+// k_pileup_solo and the read-parallel summary (bc_sum.hip): the walk's arguments and their own.
+struct PileArgs : TileArgs {
     int64_t tiles_per_wave;  // k_pileup_solo: consecutive tiles swept by one wave
     // k_pileup_solo with summary partials (bc_pileup_partials): for every quarter (2048
     // positions, a subtree of numpy's pairwise tree) of the whole buffers [0, full_chunks), its
@@ -72,16 +82,13 @@ struct PileArgs {
     long long* dcov;
     int64_t nleaf;
     int64_t n_tail_tiles;  // tiles of the last partial buffer (k_sum_exact's first work items)
-    int ablate;  // diagnostic only (BC_ABLATE): 1 no reads, 2 no search, 4 no walk, 8 no stats
-                 // math, 16 no stores, 32 no sequence staging
-    unsigned long long* trace;  // diagnostic only (BC_TRACE): per-wave phase stamps, else null
 };
 
 // Diagnostic phase stamps (BC_TRACE builds the buffer; null otherwise): s_memrealtime (100 MHz,
 // chip-wide) of phase `ph` of this wave, written by lane 0 with a vector store.
 constexpr int kTracePhases = 12;
 // Compiled in only with -DBC_PHASE_TRACE (scripts/trace_phases.py): the stamps cost registers.
-__device__ __forceinline__ void trace_stamp(const PileArgs& A, int ph) {
+__device__ __forceinline__ void trace_stamp(const TileArgs& A, int ph) {
 #ifdef BC_PHASE_TRACE
     if (A.trace && (threadIdx.x & 63) == 0)
         A.trace[((size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * kTracePhases + ph] =
@@ -227,60 +234,11 @@ __device__ __forceinline__ void count_event(uint32_t e, uint32_t byte, uint32_t 
     acc += 1ull << (ok ? col * kField : (unsigned)kJunk);
 }
 
-// Fused kernel 2, part 1: the fp64 terms -(p*log2(p)) of a tile's primary (c < K) and
-// secondary (K <= s < 2K) distributions, one per lane over the group (main.py:37-53), plus the
-// percentages.  Kept out of line: inlined, the log2 constants would be hoisted into registers
-// for the whole kernel and push the read walk into spills.
-template <int K>
-__device__ __attribute__((noinline)) void tile_terms(const PileArgs& A, const uint32_t* fin_g, double* terms_g,
-                                                     int64_t t0, int first, int stride) {
-    const int64_t L = A.L;
-    for (int slot = first; slot < 2 * K * kTile; slot += stride) {
-        // slot order A C G T, A2 C2 G2 T2, DS DS2 [N N2]: the deletion / N columns, zero in most
-        // batches, fall in the last (partial) round of the group's lanes
-        const int q = slot / kTile, p = slot % kTile;
-        const int sc = q < 4 ? q : (q < 8 ? K + q - 4 : 4 + ((q - 8) >> 1) + ((q - 8) & 1) * K);
-        const int64_t Pp = t0 + p;
-        if (Pp >= L) continue;
-        uint32_t c[6];
-        int64_t cov = 0;
-        int am = 0;
-#pragma unroll
-        for (int j = 0; j < K; ++j) {
-            c[j] = fin_g[j * kTile + p];
-            cov += c[j];
-            if (c[j] > c[am]) am = j;  // np.argmax: first maximum
-        }
-        double term = 0.0;
-        if (sc < K) {
-            if (cov != 0) {
-                if (c[sc] != 0) {
-                    const double pj = (double)c[sc] / (double)cov;
-                    if (A.pc) A.pc[(int64_t)sc * L + Pp] = 100.0 * pj;
-                    term = -(pj * glibc_log2(pj));
-                } else if (A.pc) {
-                    A.pc[(int64_t)sc * L + Pp] = 0.0;  // 100 * (0 / cov), exactly
-                }
-            } else if (A.pc) {
-                A.pc[(int64_t)sc * L + Pp] = -1.0;
-            }
-        } else {
-            const int j = sc - K;
-            const int64_t cov2 = cov - c[am];
-            if (cov2 != 0 && j != am && c[j] != 0) {
-                const double q = (double)c[j] / (double)cov2;
-                term = -(q * glibc_log2(q));
-            }
-        }
-        terms_g[sc * kTile + p] = term;
-    }
-}
-
 // Complex chunks (a read with more than 8 CIGAR ops, more than 4 runs or huge indels): lanes own
 // positions, each read of the chunk is resolved at the lane's position by walking its CIGAR
 // from memory (records in LDS hold absolute sequence nibble indices), kBatch reads at a time.
 template <bool QUAL>
-__device__ __forceinline__ void walk_complex(const PileArgs& A, const uint4* rec, int nr, int64_t P, int64_t t0,
+__device__ __forceinline__ void walk_complex(const TileArgs& A, const uint4* rec, int nr, int64_t P, int64_t t0,
                                              int64_t rbase, bool beyond, uint32_t mcn, uint32_t mcb,
                                              unsigned long long& acc, int64_t& bad) {
     const uint8_t* sp = A.seq ? A.seq : (const uint8_t*)A.pos;  // never dereferenced at a bad index
@@ -322,7 +280,7 @@ __device__ __forceinline__ void walk_complex(const PileArgs& A, const uint4* rec
 // rounding the steps up to even only ever touches padding records).  NR: the chunk's largest
 // run count (1, 2, 4).  nr and it4 are wave-uniform.
 template <int NR, bool GAP, bool STAGED, bool QUAL, int NC>
-__device__ __forceinline__ void walk_swar(const PileArgs& A, const uint4* rec, const uint32_t* words, int nr, int gb,
+__device__ __forceinline__ void walk_swar(const TileArgs& A, const uint4* rec, const uint32_t* words, int nr, int gb,
                                           int s8, int64_t rbase, bool edge, uint32_t bmask, Swar& W, int& it4,
                                           uint32_t (&cnt)[6], int64_t& bad) {
     const SeqSrc src{words, STAGED ? (int64_t)(kStage / 4) : A.seq_words, A.qual, A.qual_bytes, A.mbq};
@@ -347,23 +305,23 @@ __device__ __forceinline__ void walk_swar(const PileArgs& A, const uint4* rec, c
     }
 }
 
-constexpr int kFinBytes = 4 * 6 * kTile * 4;
+constexpr int kFinBytes = 6 * kTile * 4;  // a group's reduced counts
+constexpr int kLog2TabBytes = 64 * 4 * 8;  // log2d::kTab
 
-// dynamic LDS: [rec: nw x 3 KB][stage: nw x kStageRegion][fin: 6 KB].  Once a tile's walk is
-// done, a wave's stage region holds its partial counts for the group reduction, and the first
-// wave's region of a group then holds the group's fp64 terms (12 x 64 x 8 B).
+// dynamic LDS of k_pileup: [rec: nw x 3 KB][stage: nw x kStageRegion][fin: groups x 1.5 KB]
+// [the log2 table: 2 KB].  fin[g] collects the counts of group g's tile (LDS atomics) and is what
+// the statistics tail reads.  Two 8-wave blocks fit a CU's 160 KiB.
 constexpr int kRecBytes = kTile * 3 * 16;
-static_assert(12 * kTile * 8 <= kStageRegion, "terms must fit a stage region");
+static_assert(2 * (8 * (kRecBytes + kStageRegion) + kFinBytes + kLog2TabBytes) <= 160 * 1024, "2 blocks per CU");
 __host__ __device__ inline size_t pileup_lds_bytes(int nw, int groups) {
-    (void)groups;
-    return (size_t)nw * (kRecBytes + kStageRegion) + kFinBytes;
+    return (size_t)nw * (kRecBytes + kStageRegion) + (size_t)groups * kFinBytes + kLog2TabBytes;
 }
 
 // Per-read fields of a chunk (lane = read), loaded one chunk ahead of their use.
 struct ReadFields {
     uint32_t pos, cb, cn, sn;
 };
-__device__ __forceinline__ ReadFields load_fields(const PileArgs& A, int64_t base, int nr, int lane) {
+__device__ __forceinline__ ReadFields load_fields(const TileArgs& A, int64_t base, int nr, int lane) {
     ReadFields f{0u, 0u, 0u, 0u};
     if (lane < nr) {
         const int64_t r = base + lane;
@@ -379,7 +337,7 @@ __device__ __forceinline__ ReadFields load_fields(const PileArgs& A, int64_t bas
 // bases below min_base_quality (count.cpp:56).  Used with a quality threshold only (LDS-DMA
 // cannot apply the mask).
 template <bool QUAL>
-__device__ __forceinline__ void stage_regs(const PileArgs& A, uint8_t* mystage, uint32_t seg_lo, uint32_t seg_hi,
+__device__ __forceinline__ void stage_regs(const TileArgs& A, uint8_t* mystage, uint32_t seg_lo, uint32_t seg_hi,
                                            int lane, bool qual_vec) {
     for (uint32_t off = lane * 16u; off < seg_hi - seg_lo; off += 1024u) {
         uint4 v = *(const uint4*)(A.seq + seg_lo + off);  // padded buffer: in bounds
@@ -422,7 +380,7 @@ constexpr uint32_t kSpecSlack = 128;  // bytes staged beyond the last read's fir
 // issued together with the CIGAR loads, so a chunk costs one memory round trip before its walk;
 // the exact segment, known after the decode, is restaged only when it is not covered.
 template <bool QUAL, int K>
-__device__ __forceinline__ void process_chunk(const PileArgs& A, int64_t base, int nr, ReadFields& F,
+__device__ __forceinline__ void process_chunk(const TileArgs& A, int64_t base, int nr, ReadFields& F,
                                               int64_t next_base, int next_nr, int lane, int s8, int gb, int64_t t0,
                                               int64_t P, bool edge, bool beyond, uint32_t bmask, uint4* myrec,
                                               uint8_t* mystage, bool qual_vec, Swar& W, int& it4, uint32_t (&cnt)[6],
