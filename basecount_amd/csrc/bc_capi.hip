@@ -589,6 +589,56 @@ int bc_pileup(bc_ctx* c, const bc_reads* r, int64_t L, uint32_t mbq, int k, doub
     return BC_OK;
 }
 
+int bc_segments_layout(const int64_t* ref_lens, int n, int64_t* voff) {
+    if (!ref_lens || !voff) return fail(BC_E_ARG, "NULL argument");
+    if (n <= 0) return fail(BC_E_ARG, "bc_segments_layout: n must be > 0");
+    const int64_t cap = BC_SEGMENTS_MAX_LEN;  // starts are int32
+    int64_t off = 0;
+    voff[0] = 0;
+    for (int i = 0; i < n; ++i) {
+        if (ref_lens[i] <= 0) return fail(BC_E_ARG, "bc_segments_layout: segment " + std::to_string(i) + ": length <= 0");
+        if (ref_lens[i] > cap - off) return fail(BC_E_ARG, "bc_segments_layout: the virtual reference exceeds 2^31 - 128");
+        off += (ref_lens[i] + 63) / 64 * 64;  // (<= 2^31 - 65 here)
+        if (off > cap) return fail(BC_E_ARG, "bc_segments_layout: the virtual reference exceeds 2^31 - 128");
+        voff[i + 1] = off;
+    }
+    return BC_OK;
+}
+
+int bc_pileup_segments(bc_ctx* c, const bc_reads* r, int n_seg, const int64_t* d_ref_len, const int64_t* d_read_beg,
+                       const int64_t* d_voff, int64_t virt_len, int32_t* d_vpos, uint32_t mbq, int k, double nf,
+                       double nf2, int32_t* d_counts, int32_t* d_cov, double* d_pc, double* d_ent, double* d_sec,
+                       double* d_sum) {
+    if (!c || !r) return fail(BC_E_ARG, "NULL argument");
+    if (n_seg <= 0) return fail(BC_E_ARG, "bc_pileup_segments: n_seg must be > 0");
+    if (!d_ref_len || !d_read_beg || !d_voff) return fail(BC_E_ARG, "bc_pileup_segments: NULL segment table");
+    if (virt_len <= 0 || virt_len % 64 || virt_len > BC_SEGMENTS_MAX_LEN)
+        return fail(BC_E_ARG, "bc_pileup_segments: virt_len must be bc_segments_layout's voff[n_seg]");
+    if (r->n_reads < 0) return fail(BC_E_ARG, "n_reads < 0");
+    if (r->n_reads > 0 && (!r->pos || !d_vpos)) return fail(BC_E_ARG, "bc_pileup_segments: NULL pos / d_vpos");
+    DeviceGuard g(c->device);
+    {
+        Timed tm(c, BC_K_INDEX);
+        HIP_TRY(bc::launch_seg_vpos(c->stream, r->pos, r->n_reads, d_ref_len, d_read_beg, d_voff, n_seg, d_vpos));
+    }
+    // the group's reads as one sorted batch on the virtual reference: no index (none was built for
+    // these starts), every read ends inside it
+    bc_reads v = *r;
+    v.pos = d_vpos;
+    v.sorted = 1;
+    v.max_end = virt_len;
+    v.tile_reads = nullptr;
+    v.n_tiles = 0;
+    v.read_runs = nullptr;
+    v.run_chunks = 0;
+    v.index_tag = 0;
+    const int rc = bc_pileup(c, &v, virt_len, mbq, k, nf, nf2, d_counts, d_cov, d_pc, d_ent, d_sec);
+    if (rc != BC_OK || !d_sum) return rc;
+    Timed tm(c, BC_K_SUMMARY);
+    HIP_TRY(bc::launch_sum_segments(c->stream, n_seg, d_ref_len, d_voff, d_cov, d_ent, d_sum));
+    return BC_OK;
+}
+
 // grow-only context scratch (a synchronizing allocation when it grows: outside graph capture)
 static int out_scratch(bc_ctx* c, size_t need) {
     if (need <= c->out_scratch_bytes) return BC_OK;

@@ -169,4 +169,12 @@ hipError_t launch_stats_leaves(hipStream_t s, int32_t* hist, int64_t L, int k, d
 hipError_t launch_tail(hipStream_t s, const int32_t* cov, const double* ent, const double* sec, int64_t L, void* work,
                        double* out, const int64_t* lo, const int64_t* hi, int n_tiles, double* amp);
 
+// ---- several references as one virtual reference (bc_segments.hip, bc_pileup_segments) ----
+// vpos[i] = voff[segment of read i] + pos[i], the segment found in read_beg[0..n_seg]
+hipError_t launch_seg_vpos(hipStream_t s, const int32_t* pos, int64_t n, const int64_t* ref_len,
+                           const int64_t* read_beg, const int64_t* voff, int n_seg, int32_t* vpos);
+// bc_summary's 4 doubles of every segment's slice [voff[i], voff[i] + ref_len[i]) into out[i][4]
+hipError_t launch_sum_segments(hipStream_t s, int n_seg, const int64_t* ref_len, const int64_t* voff,
+                               const int32_t* cov, const double* ent, double* out);
+
 }  // namespace bc

@@ -102,6 +102,9 @@ def lib() -> C.CDLL:
         "bc_pileup_partials": ([vp, C.POINTER(BcReads), i64, u32, C.c_int, dbl, dbl, vp, vp, vp, vp, vp,
                                 vp], C.c_int),
         "bc_summary_fold": ([vp, C.c_int, vp, vp, vp], C.c_int),
+        "bc_segments_layout": ([vp, C.c_int, vp], C.c_int),
+        "bc_pileup_segments": ([vp, C.POINTER(BcReads), C.c_int, vp, vp, vp, i64, vp, u32, C.c_int, dbl, dbl,
+                                vp, vp, vp, vp, vp, vp], C.c_int),
         "bc_graph_begin": ([vp], C.c_int),
         "bc_graph_end": ([vp, C.POINTER(vp)], C.c_int),
         "bc_graph_launch": ([vp, vp], C.c_int),
@@ -348,6 +351,17 @@ class Context:
         oa = (C.c_void_p * max(1, n))(*outs)
         check(lib().bc_summary_fold(self.h, n, la, wa, oa))
 
+    def pileup_segments(self, reads, n_seg, d_ref_len, d_read_beg, d_voff, virt_len, d_vpos, mbq, k, nf, nf2,
+                        d_counts, d_cov, d_pc, d_ent, d_sec, d_sum=None) -> None:
+        """bc_pileup_segments: n_seg references as one virtual reference of virt_len positions
+        (segments_layout), one pileup launch; ``reads`` carries the original starts, the device
+        table (d_ref_len, d_read_beg, d_voff: int64) says which reads are whose.  d_sum: [n_seg][4]
+        doubles (bc_summary per segment) or None."""
+        r = reads.r if isinstance(reads, DeviceReads) else reads
+        check(lib().bc_pileup_segments(self.h, C.byref(r), int(n_seg), d_ref_len, d_read_beg, d_voff,
+                                       int(virt_len), d_vpos, int(mbq), int(k), float(nf), float(nf2),
+                                       d_counts, d_cov, d_pc, d_ent, d_sec, d_sum))
+
     def capture(self, fn) -> "Graph":
         """Record the compute calls made by fn() into a hipGraph (replay with Graph.launch)."""
         check(lib().bc_graph_begin(self.h))
@@ -436,3 +450,13 @@ def seq_event_bytes(seq_bytes: int) -> int:
 
 def summary_work_bytes(L: int) -> int:
     return int(lib().bc_summary_work_bytes(int(L)))
+
+
+def segments_layout(ref_lens) -> np.ndarray:
+    """bc_segments_layout: the virtual offsets int64 [n + 1] of n references placed one after the
+    other, each on a 64-position boundary (host arithmetic, no GPU); BcError (BC_E_ARG) for an
+    empty list, a length <= 0 or a total past 2^31 - 128."""
+    a = np.ascontiguousarray(ref_lens, np.int64)
+    out = np.zeros(a.size + 1, np.int64)
+    check(lib().bc_segments_layout(a.ctypes.data if a.size else None, int(a.size), out.ctypes.data))
+    return out

@@ -476,7 +476,14 @@ class _BatchOnDevice:
         self.d_sn = scratch.get("b_sn", max(4, 4 * m)).upload(sel.seq_nib)
 
     def reads(self, t: int) -> D.BcReads:
-        b0, b1 = int(self.sel.ref_beg[t]), int(self.sel.ref_beg[t + 1])
+        return self._slice(int(self.sel.ref_beg[t]), int(self.sel.ref_beg[t + 1]))
+
+    def reads_run(self, t_first: int, t_last: int) -> D.BcReads:
+        """The reads of the consecutive references t_first .. t_last as one slice, with their own
+        starts (bc_pileup_segments moves them to the group's virtual reference)."""
+        return self._slice(int(self.sel.ref_beg[t_first]), int(self.sel.ref_beg[t_last + 1]))
+
+    def _slice(self, b0: int, b1: int) -> D.BcReads:
         r = D.BcReads()
         r.n_reads = b1 - b0
         r.pos = self.d_pos.ptr + 4 * b0
@@ -507,6 +514,98 @@ def batch_records(chunk_size: int) -> int:
         return max(1, int(v))
     cs = int(chunk_size)
     return min(max(cs, 1 << 16), 1 << 24) if cs > 0 else 1 << 22
+
+
+# ------------------------------------------------------------------------- grouped references
+# Many small references (a transcriptome, a plasmid panel, the short contigs of GRCh38): counting
+# them one launch and one blocking download each costs R x (launch + host round trips) for
+# kernels of microseconds.  The complete, well-formed references of a batch that are consecutive
+# in refID order are counted as ONE virtual reference instead (bc_pileup_segments).
+GROUP_MAX_LEN = 1 << 22  # longer references keep the per-reference path (they fill the device alone)
+GROUP_CAP_DEFAULT = 1 << 24  # virtual positions per group: ~1.4 GB of row outputs
+
+# the last get_basecounts call's routing (tests, scripts/many_refs.py): the groups (reference
+# names, in refID order) and the references that took the per-reference path
+PLAN: dict = {"groups": [], "single": []}
+
+
+def group_cap() -> int:
+    """Virtual positions a group may span (BASECOUNT_GROUP_MAX); 0: grouping is off
+    (BASECOUNT_GROUP_REFS=0)."""
+    if os.environ.get("BASECOUNT_GROUP_REFS", "1") == "0":
+        return 0
+    v = os.environ.get("BASECOUNT_GROUP_MAX")
+    return min(max(64, int(v)), 2**31 - 128) if v else GROUP_CAP_DEFAULT
+
+
+def plan_groups(lengths_by_tid, eligible_by_tid, cap: int, first: int = 0) -> list:
+    """The groups of a batch: maximal runs of consecutive eligible refIDs (file order), cut so that
+    each run's sum of round_up(L, 64) stays within ``cap``; runs of one reference are dropped (that
+    reference keeps the per-reference path).  The two sequences are indexed by refID - ``first``;
+    returns lists of refIDs.  Pure: nothing here depends on the order references are reported in."""
+    groups, run, size = [], [], 0
+    for i, (L, ok) in enumerate(zip(lengths_by_tid, eligible_by_tid)):
+        v = (int(L) + 63) // 64 * 64
+        if not ok or v > cap:
+            if len(run) > 1:
+                groups.append(run)
+            run, size = [], 0
+            continue
+        if run and size + v > cap:
+            if len(run) > 1:
+                groups.append(run)
+            run, size = [], 0
+        run.append(first + i)
+        size += v
+    if len(run) > 1:
+        groups.append(run)
+    return groups
+
+
+def _reads_inside(pos, span, ref_beg, lengths_t) -> np.ndarray:
+    """Per refID: its reads of the batch start in non-decreasing order and every one of them lies
+    inside the reference (0 <= pos, pos + span <= L), so that none can reach a neighbour of a group
+    or raise the reference's IndexError."""
+    nper = np.diff(ref_beg)
+    tid = np.repeat(np.arange(nper.size), nper)
+    p = pos.astype(np.int64)
+    bad = (p < 0) | (p + span > lengths_t[tid])
+    if p.size > 1:
+        bad[1:] |= (p[1:] < p[:-1]) & (tid[1:] == tid[:-1])
+    ok = np.ones(nper.size, bool)
+    ok[tid[bad]] = False
+    return ok
+
+
+def _device_group(ctx, reads, lens, read_beg, mbq, k, nf, nf2, mode, scratch) -> list:
+    """One launch and one download per output array for a group of references (their lengths
+    ``lens``; reads [read_beg[i], read_beg[i + 1]) of ``reads`` are reference i's): each
+    reference's result as _device_reference gives it, sliced on the host."""
+    n = len(lens)
+    voff = D.segments_layout(lens)
+    Lv = int(voff[-1])
+    table = np.concatenate([np.asarray(lens, np.int64), np.asarray(read_beg, np.int64), voff])
+    d_tab = scratch.get("seg_table", table.nbytes).upload(table)
+    d_vpos = scratch.get("seg_vpos", 4 * max(1, int(reads.n_reads)))
+    rows = mode == "rows"
+    outs = scratch.outputs(k, Lv, want_pc=rows)
+    hist = scratch.get("hist", 4 * k * Lv)
+    d_sum = None if rows else scratch.get("seg_sum", 32 * n)
+    ctx.pileup_segments(reads, n, d_tab.ptr, d_tab.ptr + 8 * n, d_tab.ptr + 8 * (2 * n + 1), Lv, d_vpos.ptr, mbq,
+                        k, nf, nf2, hist.ptr, outs["cov"].ptr, outs["pc"].ptr if rows else None,
+                        outs["ent"].ptr, outs["sec"].ptr, d_sum.ptr if d_sum is not None else None)
+    if not rows:
+        s = d_sum.download(np.float64, 4 * n).reshape(n, 4)
+        return [{"L": int(L), "avg_cov": np.float64(s[i, 0]), "avg_ent": np.float64(s[i, 1]), "nnz": int(s[i, 2])}
+                for i, L in enumerate(lens)]
+    counts = hist.download(np.int32, k * Lv).reshape(k, Lv)
+    d = _download(outs, counts, k, Lv)
+    out = []
+    for i, L in enumerate(lens):
+        sl = slice(int(voff[i]), int(voff[i]) + int(L))
+        out.append(RefData(np.ascontiguousarray(d.counts[:, sl]), np.ascontiguousarray(d.pc[:, sl]),
+                           d.ent[sl].copy(), d.sec[sl].copy(), d.cov[sl].copy()))
+    return out
 
 
 # Host buffers released at the end of the CLI run instead of when the stream ends: giving back a
@@ -602,6 +701,7 @@ def _get_basecounts(bam, references, min_base_quality, min_mapping_quality, chun
         references = get_references(stream, references)
         names = stream.references
         ref_index = {n: i for i, n in enumerate(names)}
+        lens_t = np.asarray(stream.lengths, np.int64)  # by refID
         reference_lengths = {ref: stream.lengths[names.index(ref)] for ref in references}
         ref_order = list(references)
         if _group is not None:
@@ -672,9 +772,39 @@ def _get_basecounts(bam, references, min_base_quality, min_mapping_quality, chun
         ctx = context(device) if (mbq_ok and (mine or split)) else None
         scratch = _scratch(ctx) if ctx is not None else None
         nf, nf2 = norm_factors(k)
+        # grouped references (plan_groups): this rank's own complete references of a file grouped by
+        # reference, for rows and plain --summarise (the amplicon windows keep the per-reference path)
+        cap = group_cap() if (ctx is not None and grouped and _tiles is None) else 0
+        PLAN["groups"], PLAN["single"] = [], []
 
         def tiles_of(ref):
             return _tiles(ref) if _tiles else None
+
+        def run_group(tids, reads, read_beg):
+            res = _device_group(ctx, reads, [int(lens_t[t]) for t in tids], read_beg, mbq, k, nf, nf2, _mode,
+                                scratch)
+            for t, r in zip(tids, res):
+                results[names[t]] = r
+                finished.add(names[t])
+            PLAN["groups"].append([names[t] for t in tids])
+
+        def batch_groups(sel, nsel, bod, here):
+            """The groups among the references of this batch: those with reads here, and the
+            requested ones between them that have none (in a sorted file they have none at all; if
+            one's reads do come later, the file is not grouped by reference and the run restarts)."""
+            ts = [ref_index[r] for r in here]
+            t_a, t_b = min(ts), max(ts)
+            elig = np.zeros(t_b - t_a + 1, bool)
+            for t in range(t_a, t_b + 1):
+                ref = names[t]
+                elig[t - t_a] = (
+                    wanted[t] and t in mine_t and ref not in split and ref not in acc and ref not in results
+                    and 0 < lens_t[t] <= GROUP_MAX_LEN
+                    and (nsel is None or int(nsel.ref_beg[t + 1]) == int(nsel.ref_beg[t])))
+            if int(elig.sum()) < 2:
+                return []
+            elig &= _reads_inside(bod.pos, bod.span, sel.ref_beg, lens_t)[t_a:t_b + 1]
+            return plan_groups(lens_t[t_a:t_b + 1], elig, cap, first=t_a)
 
         base = 0  # accepted reads before the current batch (global ordinals; sharded: in the range)
         cur = nxt = None
@@ -738,7 +868,17 @@ def _get_basecounts(bam, references, min_base_quality, min_mapping_quality, chun
                         bod = _BatchOnDevice(ctx, f, sel, need_qual=mbq > 0, scratch=scratch)
                     t_refs = _phase("kernels + download")
                     t_refs.__enter__()
+                    in_group = set()
+                    if cap and len(here) > 1:
+                        for tids in batch_groups(sel, nsel, bod, here):
+                            b0 = int(sel.ref_beg[tids[0]])
+                            run_group(tids, bod.reads_run(tids[0], tids[-1]),
+                                      [int(sel.ref_beg[t]) - b0 for t in tids] + [int(sel.ref_beg[tids[-1] + 1]) - b0])
+                            in_group.update(names[t] for t in tids)
                     for ref in here:
+                        if ref in in_group:  # (cannot have a range fault: every read lies inside)
+                            continue
+                        PLAN["single"].append(ref)
                         t = ref_index[ref]
                         L = int(reference_lengths[ref])
                         # (a reference split over ranks is never complete on one: accumulated)
@@ -778,9 +918,19 @@ def _get_basecounts(bam, references, min_base_quality, min_mapping_quality, chun
                 if ref in acc:
                     split_acc[ref] = acc.pop(ref)
             if ctx is not None and fl.inloop() is None:
+                if cap:
+                    # the requested references that never had a read, grouped like the others: one
+                    # launch with no reads per group instead of one per reference
+                    empty = np.zeros(len(names), bool)
+                    for ref in mine:
+                        if ref not in results and ref not in split and ref not in acc:
+                            empty[ref_index[ref]] = 0 < lens_t[ref_index[ref]] <= GROUP_MAX_LEN
+                    for tids in plan_groups(lens_t, empty, cap) if int(empty.sum()) > 1 else []:
+                        run_group(tids, _no_reads(), [0] * (len(tids) + 1))
                 for ref in mine:
                     if ref in results or ref in split:
                         continue
+                    PLAN["single"].append(ref)
                     L = int(reference_lengths[ref])
                     if ref in acc:
                         results[ref] = _finish_reference(ctx, acc.pop(ref), L, ncols, k, nf, nf2, _mode,

@@ -236,6 +236,48 @@ int bc_pileup(bc_ctx* ctx, const bc_reads* d_reads, int64_t ref_len, uint32_t mi
               double nf, double nf2, int32_t* d_counts, int32_t* d_cov, double* d_pc, double* d_ent,
               double* d_sec);
 
+/* Several small references of one file in ONE launch (a transcriptome, a plasmid panel, the short
+ * contigs of an assembly): the segmented pileup.
+ * A coordinate-sorted file orders reads by (refID, pos).  Reference i of a group of n consecutive
+ * references is placed at virtual offset voff[i] = sum_{j<i} round_up(ref_len[j], 64); with
+ * voff[i] added to its reads' starts, the group's reads are one sorted batch on one virtual
+ * reference of voff[n] positions, and every 64-position tile belongs to exactly one reference.
+ * The pileup kernels run on that batch as they are; segment i's results are the slices
+ * [voff[i], voff[i] + ref_len[i]) of the outputs (pad positions have coverage 0 and mean nothing).
+ *
+ * bc_segments_layout: host arithmetic only.  voff[0..n] from ref_lens[0..n); BC_E_ARG for n <= 0,
+ * a length <= 0, or voff[n] > BC_SEGMENTS_MAX_LEN (starts are int32).
+ *
+ * bc_pileup_segments enqueues, on the context's stream:
+ *   1. k_seg_vpos: d_vpos[i] = d_reads->pos[i] + voff[segment of read i] (the segment found in
+ *      d_read_beg; d_vpos: int32 [n_reads], caller-owned);
+ *   2. bc_pileup on a copy of *d_reads with pos = d_vpos, sorted = 1, max_end = virt_len and no
+ *      index, for a reference of virt_len positions: the kernel shape is chosen as for any batch
+ *      (bc_ctx_set_shape honoured); outputs as bc_pileup's, at virtual size (d_counts [k][virt_len],
+ *      d_cov, d_pc or NULL, d_ent, d_sec);
+ *   3. when d_sum != NULL, k_sum_segments: d_sum[i][0..4) = bc_summary's four doubles of segment
+ *      i's slice, bit for bit (one workgroup per segment, one launch).
+ * d_reads: the group's reads in file order with their ORIGINAL starts (max_span truthful; sorted,
+ * max_end and the index fields are ignored); n_reads may be 0 (every segment empty).
+ * The segment table is three device arrays the caller uploaded: d_ref_len [n_seg], d_read_beg
+ * [n_seg + 1] (segment i's reads are [read_beg[i], read_beg[i + 1]) of d_reads; read_beg[0] = 0,
+ * read_beg[n_seg] = n_reads; empty segments allowed), d_voff [n_seg + 1] as bc_segments_layout
+ * gives it, virt_len = voff[n_seg].
+ * Contract: every read lies inside its segment, 0 <= pos and pos + span <= ref_len, and each
+ * segment's starts are non-decreasing.  No range error can then occur (bc_range_error stays -1).  A
+ * caller that breaks this gets counts in a pad or in a neighbouring segment, never an access
+ * outside the buffers: starts are clamped into [0, ref_len] of their segment, and everything past
+ * that is the kernels' own edge logic on [0, virt_len).
+ * Stream-ordered and capturable like bc_pileup: no synchronisation, and no allocation except the
+ * k_rc scratch growing on first use (make that first call outside a graph capture).
+ * Timed as BC_K_INDEX (k_seg_vpos), the pileup's own ids, and BC_K_SUMMARY (k_sum_segments).  */
+#define BC_SEGMENTS_MAX_LEN 2147483520 /* 2^31 - 128 */
+int bc_segments_layout(const int64_t* ref_lens, int n, int64_t* voff /* [n + 1] */);
+int bc_pileup_segments(bc_ctx* ctx, const bc_reads* d_reads, int n_seg, const int64_t* d_ref_len,
+                       const int64_t* d_read_beg, const int64_t* d_voff, int64_t virt_len, int32_t* d_vpos,
+                       uint32_t min_base_quality, int k, double nf, double nf2, int32_t* d_counts, int32_t* d_cov,
+                       double* d_pc, double* d_ent, double* d_sec, double* d_sum /* [n_seg][4] or NULL */);
+
 /* hipGraph capture of a sequence of compute calls on the context's stream (the context must own
  * its stream or have been given a non-default one).  bc_graph_end instantiates the graph;
  * bc_graph_launch replays it on the context's stream.                                         */
