@@ -58,6 +58,17 @@ struct DeviceGuard {
     }
 };
 
+// Kernel 1 of the deep / long-span paths (use_rc): the read-chunked k_rc, or under BC_SHAPE_OPS
+// the scan-expanded k_ops (timed as BC_K_COUNT), atomics into `counts`
+hipError_t launch_chunked(bc_ctx* c, const bc_reads& r, int64_t L, uint32_t mbq, int k, int32_t* counts) {
+    if (c->shape == BC_SHAPE_OPS) {
+        Timed tm(c, BC_K_COUNT);
+        return bc::launch_ops(c->stream, r, L, mbq, k, counts, c->d_err, c->reads_per_block);
+    }
+    Timed tm(c, BC_K_RC);
+    return bc::launch_rc(c->stream, r, L, mbq, k, counts, c->d_err);
+}
+
 // Reads per kernel-1 workgroup: enough workgroups to fill 256 CUs several times over, and few
 // enough reads per chunk that a sorted chunk's positions fit one LDS window.
 int choose_rpb(int64_t n, int64_t L, int max_span, int sorted, int forced) {
@@ -98,6 +109,7 @@ std::pair<int, int64_t> host_spans(const bc_reads& r) {
 int index_what(const bc_ctx* c, const bc_reads& r, int64_t L, int what = BC_INDEX_AUTO) {
     if (!(what & BC_INDEX_AUTO)) return what & (BC_INDEX_RUNS | BC_INDEX_TILES);
     if (!r.sorted || r.n_reads <= 0 || r.seq_layout != BC_SEQ_EVENT) return 0;
+    if (c->shape == BC_SHAPE_OPS) return 0;  // k_ops reads no index
     if (bc::use_rc(r, L, c->shape)) return BC_INDEX_RUNS;
     return bc::pileup_is_solo(r, L, c->shape, c->tile_waves) ? 0 : BC_INDEX_TILES;
 }
@@ -276,7 +288,7 @@ int bc_ctx_stream(bc_ctx* c, void** s) {
 
 int bc_ctx_set_shape(bc_ctx* c, int shape, int tile_waves, int rpb) {
     if (!c) return fail(BC_E_ARG, "ctx is NULL");
-    if (shape < BC_SHAPE_AUTO || shape > BC_SHAPE_TILE_NO_SOLO) return fail(BC_E_ARG, "unknown BC_SHAPE_* value");
+    if (shape < BC_SHAPE_AUTO || shape > BC_SHAPE_OPS) return fail(BC_E_ARG, "unknown BC_SHAPE_* value");
     if (tile_waves != 0 && tile_waves != 1 && tile_waves != 2 && tile_waves != 4 && tile_waves != 8)
         return fail(BC_E_ARG, "tile_waves must be 0, 1, 2, 4 or 8");
     if (rpb < 0 || rpb > 32768) return fail(BC_E_ARG, "reads_per_block must be 0..32768");
@@ -527,9 +539,13 @@ int bc_count(bc_ctx* c, const bc_reads* r, int64_t ref_len, uint32_t mbq, int nc
     if (mbq > 0 && !r->qual) return fail(BC_E_ARG, "min_base_quality > 0 needs qualities");
     DeviceGuard g(c->device);
     const bool event = r->seq_layout == BC_SEQ_EVENT && !((uintptr_t)r->seq & 15u);
+    if (c->shape == BC_SHAPE_OPS && r->seq_layout == BC_SEQ_EVENT) {
+        // k_ops reads bases one by one: sorted or not, any sequence alignment
+        HIP_TRY(launch_chunked(c, *r, ref_len, mbq, ncols, d_hist));
+        return BC_OK;
+    }
     if (r->sorted && event && bc::use_rc(*r, ref_len, c->shape)) {
-        Timed tm(c, BC_K_RC);
-        HIP_TRY(bc::launch_rc(c->stream, *r, ref_len, mbq, ncols, d_hist, c->d_err));
+        HIP_TRY(launch_chunked(c, *r, ref_len, mbq, ncols, d_hist));
         return BC_OK;
     }
     if (r->sorted && r->max_span <= bc::kTileMaxSpan && event) {
@@ -575,10 +591,7 @@ int bc_pileup(bc_ctx* c, const bc_reads* r, int64_t L, uint32_t mbq, int k, doub
             c->rc_scratch_bytes = need;
             HIP_TRY(hipMemsetAsync(c->rc_scratch, 0, need, c->stream));
         }
-        {
-            Timed tm(c, BC_K_RC);
-            HIP_TRY(bc::launch_rc(c->stream, *r, L, mbq, k, c->rc_scratch, c->d_err));
-        }
+        HIP_TRY(launch_chunked(c, *r, L, mbq, k, c->rc_scratch));
         Timed tm(c, BC_K_STATS);
         HIP_TRY(bc::launch_stats(c->stream, c->rc_scratch, L, k, nf, nf2, d_cov, d_pc, d_ent, d_sec, d_counts));
         return BC_OK;
@@ -980,10 +993,7 @@ int bc_pileup_summary_amplicons(bc_ctx* c, const bc_reads* r, int64_t L, uint32_
         c->rc_scratch_bytes = need;
         HIP_TRY(hipMemsetAsync(c->rc_scratch, 0, need, c->stream));
     }
-    {
-        Timed tm(c, BC_K_RC);
-        HIP_TRY(bc::launch_rc(c->stream, *r, L, mbq, k, c->rc_scratch, c->d_err));
-    }
+    HIP_TRY(launch_chunked(c, *r, L, mbq, k, c->rc_scratch));
     {
         Timed tm(c, BC_K_STATS);
         HIP_TRY(bc::launch_stats_leaves(c->stream, c->rc_scratch, L, k, nf, nf2, d_cov, d_ent, d_sec, d_counts, d_work));

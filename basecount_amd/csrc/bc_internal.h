@@ -102,6 +102,11 @@ hipError_t launch_sum_sparse(hipStream_t s, const bc_reads& r, int64_t L, uint32
                              unsigned long long* d_err, SumParts& parts, void* scratch, size_t scratch_bytes);
 hipError_t launch_rc(hipStream_t s, const bc_reads& r, int64_t L, uint32_t mbq, int ncols, int32_t* counts,
                      unsigned long long* d_err);
+// k_ops (bc_ops.hip, BC_SHAPE_OPS): launch_rc's contract for batches of many-op reads, sorted or
+// not; reads_per_block 0 = from the batch (ops_reads_per_block), else 1..32768
+int ops_reads_per_block(const bc_reads& r, int64_t L, int forced);
+hipError_t launch_ops(hipStream_t s, const bc_reads& r, int64_t L, uint32_t mbq, int ncols, int32_t* counts,
+                      unsigned long long* d_err, int reads_per_block);
 // bc_pileup / bc_count choose the read-chunked k_rc over the tiled k_pileup when a tile would
 // walk at least this many reads (deep batches; bc_ctx_set_shape overrides)
 constexpr double kRcMinReadsPerTile = 2048.0;

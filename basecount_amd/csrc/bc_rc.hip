@@ -1071,7 +1071,7 @@ __global__ __launch_bounds__(NT, 3) void k_rc(RcArgs A) {
 
 bool use_rc(const bc_reads& r, int64_t L, int shape) {
     if (!r.sorted || r.n_reads <= 0 || r.seq_layout != BC_SEQ_EVENT) return false;
-    if (shape == BC_SHAPE_RC) return true;
+    if (shape == BC_SHAPE_RC || shape == BC_SHAPE_OPS) return true;  // (OPS: k_ops in k_rc's place)
     if (shape == BC_SHAPE_TILE || shape == BC_SHAPE_TILE_NO_SOLO) return r.max_span > kTileMaxSpan;
     if (r.max_span > kTileMaxSpan) return true;  // the tiled kernel's look-back gets too long
     const int64_t reach = r.max_end > L ? r.max_end : L;

@@ -17,7 +17,7 @@ from ._native import _libs, _load
 BC_E_ARG, BC_E_HIP, BC_E_RANGE, BC_E_NODEV, BC_E_COMM = -1, -2, -3, -4, -5
 COMM_ID_BYTES = 128  # BC_COMM_ID_BYTES
 BC_SEQ_BAM, BC_SEQ_EVENT = 0, 1
-SHAPES = {"auto": 0, "tile": 1, "rc": 2, "tile_no_solo": 3}  # BC_SHAPE_*
+SHAPES = {"auto": 0, "tile": 1, "rc": 2, "tile_no_solo": 3, "ops": 4}  # BC_SHAPE_*
 KERNEL_NAMES = ("count", "stats", "rc", "pileup", "summary", "amplicons", "index", "solo", "sort")  # BC_K_* ids
 BC_INDEX_RUNS, BC_INDEX_TILES, BC_INDEX_AUTO = 1, 2, 4
 KERNEL_IDS = len(KERNEL_NAMES)
@@ -247,6 +247,7 @@ class Context:
         check(lib().bc_ctx_create(self.device, stream, C.byref(h)))
         self.h = h.value
         self._keep = []
+        self.shape_args = ("auto", 0, 0)  # set_shape's arguments in force
 
     def close(self):
         if self.h:
@@ -265,8 +266,11 @@ class Context:
 
     def set_shape(self, shape: str = "auto", tile_waves: int = 0, reads_per_block: int = 0) -> None:
         """Kernel-shape override for bc_count / bc_pileup (bc_ctx_set_shape): "auto", "tile",
-        "rc" or "tile_no_solo"; tile_waves 0/1/2/4/8; reads_per_block 0 or 1..32768."""
+        "rc", "tile_no_solo" or "ops" (the scan-expanded k_ops for batches of many-op reads, never
+        chosen by "auto"; bc_count under it also takes unsorted batches); tile_waves 0/1/2/4/8;
+        reads_per_block 0 or 1..32768.  ``shape_args`` keeps the arguments in force."""
         check(lib().bc_ctx_set_shape(self.h, SHAPES[shape], int(tile_waves), int(reads_per_block)))
+        self.shape_args = (shape, int(tile_waves), int(reads_per_block))
 
     def sync(self):
         check(lib().bc_sync(self.h))

@@ -22,6 +22,7 @@ replayed from the fault positions (``_first_error``).
 from __future__ import annotations
 
 import argparse
+import contextlib
 import json
 import ctypes as C
 import math
@@ -526,7 +527,46 @@ GROUP_CAP_DEFAULT = 1 << 24  # virtual positions per group: ~1.4 GB of row outpu
 
 # the last get_basecounts call's routing (tests, scripts/many_refs.py): the groups (reference
 # names, in refID order) and the references that took the per-reference path
-PLAN: dict = {"groups": [], "single": []}
+# "ops": the references (and the groups' references) whose reads took the long-read kernel shape
+PLAN: dict = {"groups": [], "single": [], "ops": []}
+
+# Long-read routing ("k_ops"): a reference's (or group's) reads take the kernel shape
+# "ops" when they are mostly many-op reads.  BASECOUNT_LONG_READS: 0 never, 1 always, otherwise the
+# rule below.  The thresholds are read off the table of scripts/long_reads.py.
+OPS_MIN_SHARE = 0.5   # share of the slice's reads with more than 8 CIGAR ops (the kernels' complex path)
+OPS_MIN_MEAN = 9.0    # mean CIGAR ops per read
+OPS_RULE_DEFAULT = True  # without the variable: the rule (True) or never (False)
+
+
+def wants_ops(cig_n) -> bool:
+    """Whether a slice of reads with these CIGAR op counts takes the shape "ops" (pure: the
+    counts and BASECOUNT_LONG_READS decide)."""
+    v = os.environ.get("BASECOUNT_LONG_READS", "")
+    if v == "0":
+        return False
+    if v == "1":
+        return True
+    if v == "" and not OPS_RULE_DEFAULT:
+        return False
+    c = np.asarray(cig_n)
+    if c.size == 0:
+        return False
+    return bool(np.mean(c > 8) >= OPS_MIN_SHARE and float(c.mean()) >= OPS_MIN_MEAN)
+
+
+@contextlib.contextmanager
+def _ops_shape(ctx, on: bool):
+    """The calls inside run under ctx.set_shape("ops") when ``on``; the shape in force before is
+    restored afterwards, also on error."""
+    if not on:
+        yield
+        return
+    prev = ctx.shape_args
+    ctx.set_shape("ops")
+    try:
+        yield
+    finally:
+        ctx.set_shape(*prev)
 
 
 def group_cap() -> int:
@@ -775,18 +815,22 @@ def _get_basecounts(bam, references, min_base_quality, min_mapping_quality, chun
         # grouped references (plan_groups): this rank's own complete references of a file grouped by
         # reference, for rows and plain --summarise (the amplicon windows keep the per-reference path)
         cap = group_cap() if (ctx is not None and grouped and _tiles is None) else 0
-        PLAN["groups"], PLAN["single"] = [], []
+        PLAN["groups"], PLAN["single"], PLAN["ops"] = [], [], []
 
         def tiles_of(ref):
             return _tiles(ref) if _tiles else None
 
-        def run_group(tids, reads, read_beg):
-            res = _device_group(ctx, reads, [int(lens_t[t]) for t in tids], read_beg, mbq, k, nf, nf2, _mode,
-                                scratch)
+        def run_group(tids, reads, read_beg, cig_n=()):
+            ops = wants_ops(cig_n)
+            with _ops_shape(ctx, ops):
+                res = _device_group(ctx, reads, [int(lens_t[t]) for t in tids], read_beg, mbq, k, nf, nf2, _mode,
+                                    scratch)
             for t, r in zip(tids, res):
                 results[names[t]] = r
                 finished.add(names[t])
             PLAN["groups"].append([names[t] for t in tids])
+            if ops:
+                PLAN["ops"].extend(names[t] for t in tids)
 
         def batch_groups(sel, nsel, bod, here):
             """The groups among the references of this batch: those with reads here, and the
@@ -873,7 +917,8 @@ def _get_basecounts(bam, references, min_base_quality, min_mapping_quality, chun
                         for tids in batch_groups(sel, nsel, bod, here):
                             b0 = int(sel.ref_beg[tids[0]])
                             run_group(tids, bod.reads_run(tids[0], tids[-1]),
-                                      [int(sel.ref_beg[t]) - b0 for t in tids] + [int(sel.ref_beg[tids[-1] + 1]) - b0])
+                                      [int(sel.ref_beg[t]) - b0 for t in tids] + [int(sel.ref_beg[tids[-1] + 1]) - b0],
+                                      bod.cig_n[b0:int(sel.ref_beg[tids[-1] + 1])])
                             in_group.update(names[t] for t in tids)
                     for ref in here:
                         if ref in in_group:  # (cannot have a range fault: every read lies inside)
@@ -884,18 +929,24 @@ def _get_basecounts(bam, references, min_base_quality, min_mapping_quality, chun
                         # (a reference split over ranks is never complete on one: accumulated)
                         closed = grouped and ref not in split and (
                             nxt is None or int(nsel.ref_beg[t + 1]) == int(nsel.ref_beg[t]))
-                        reads = _indexed(ctx, bod.reads(t), L, scratch)
                         b0 = int(sel.ref_beg[t])
+                        ops = wants_ops(bod.cig_n[b0:int(sel.ref_beg[t + 1])])
+                        if ops and ref not in PLAN["ops"]:
+                            PLAN["ops"].append(ref)
                         if closed and ref not in acc:  # the whole reference in this batch: fused
-                            results[ref], bad = _device_reference(
-                                ctx, reads, L, mbq, ncols, k, nf, nf2, _mode, tiles_of(ref),
-                                _tiles is not None, scratch)
+                            with _ops_shape(ctx, ops):
+                                reads = _indexed(ctx, bod.reads(t), L, scratch)
+                                results[ref], bad = _device_reference(
+                                    ctx, reads, L, mbq, ncols, k, nf, nf2, _mode, tiles_of(ref),
+                                    _tiles is not None, scratch)
                             finished.add(ref)
                         else:  # kernel 1 into the reference's accumulator
                             if ref not in acc:
                                 acc[ref] = ctx.alloc(max(16, 4 * ncols * L))
                                 acc[ref].zero()
-                            ctx.count(reads, L, mbq, ncols, acc[ref].ptr)
+                            with _ops_shape(ctx, ops):
+                                reads = _indexed(ctx, bod.reads(t), L, scratch)
+                                ctx.count(reads, L, mbq, ncols, acc[ref].ptr)
                             bad = ctx.range_error()
                             if closed:
                                 results[ref] = _finish_reference(ctx, acc.pop(ref), L, ncols, k, nf, nf2, _mode,

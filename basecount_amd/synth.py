@@ -135,6 +135,86 @@ def make_reads(contigs, reads_per_contig: int, mixed: bool, seed: int, read_len:
     )
 
 
+def make_long_reads(contigs, reads_per_contig: int, seed: int, mean_len: int = 500, indel_every: float = 15.0,
+                    sigma: float = 0.3, clip_frac: float = 0.3, skip_frac: float = 0.004, eqx_frac: float = 0.05,
+                    n_frac: float = 0.005, unsorted: bool = False) -> ReadSet:
+    """Nanopore-like reads: many CIGAR ops per read (about 2 * mean_len / indel_every).
+
+    Per read a target length, log-normal around ``mean_len`` (``sigma`` of the logarithm, at most a
+    third of the contig); its aligned bases come as M runs of geometric length (mean
+    ``indel_every``), a share ``eqx_frac`` of them ``=`` or ``X``, separated by an I or a D of 1-3
+    bases or, with probability ``skip_frac``, an N of 20-200.  A share ``clip_frac`` of the read
+    ends carries an S of 1-30 bases, half of those an H outside it as well.  Bases U{A,C,G,T} with
+    ``n_frac`` N, qualities U[2,40], mapq U[0,60].  Every stored length is even (the trailing S
+    takes the odd base), so qualities lie at the bases' nibble indices.  Reads come out
+    coordinate-sorted per contig unless ``unsorted``; seeded and vectorised like make_reads."""
+    rng = np.random.default_rng(seed)
+    parts = []
+    for _, L in contigs:
+        n = int(reads_per_contig)
+        target = np.exp(rng.normal(np.log(mean_len) - sigma * sigma / 2, sigma, n))
+        target = np.clip(target, 2.0, max(2.0, L / 3.0))
+        nm = np.maximum(1, rng.poisson(target / float(indel_every))).astype(np.int64)  # M runs per read
+        rid = np.repeat(np.arange(n), nm)                  # read of each M run
+        first = np.concatenate([[0], np.cumsum(nm)[:-1]])
+        within = np.arange(int(nm.sum())) - first[rid]     # run number inside its read
+        # (mean target / runs: ~indel_every, and a read of few runs still comes out near its target)
+        mlen = rng.geometric(np.minimum(1.0, nm / target)[rid]).astype(np.int64)
+        mop = np.where(rng.random(rid.size) < eqx_frac, rng.integers(7, 9, rid.size), 0)
+        # the gap after each run but a read's last: I, D or N
+        gap = within < nm[rid] - 1
+        u = rng.random(rid.size)
+        gop = np.where(u < skip_frac, 3, np.where(u < 0.5 + skip_frac / 2, 1, 2))
+        glen = np.where(gop == 3, rng.integers(20, 201, rid.size), rng.integers(1, 4, rid.size)).astype(np.int64)
+        glen = np.where(gap, glen, 0)
+        m_sum = np.bincount(rid, mlen, n).astype(np.int64)
+        i_sum = np.bincount(rid, np.where(gop == 1, glen, 0), n).astype(np.int64)
+        d_sum = np.bincount(rid, np.where(gop != 1, glen, 0), n).astype(np.int64)
+        span = m_sum + d_sum
+        if int(span.max()) > L:
+            raise ValueError("make_long_reads: a read is longer than its contig (lower mean_len)")
+        ls = np.where(rng.random(n) < clip_frac, rng.integers(1, 31, n), 0).astype(np.int64)  # leading S
+        ts = np.where(rng.random(n) < clip_frac, rng.integers(1, 31, n), 0).astype(np.int64)  # trailing S
+        ts += (ls + m_sum + i_sum + ts) & 1                # even stored length
+        lh = np.where((ls > 0) & (rng.random(n) < 0.5), rng.integers(1, 21, n), 0).astype(np.int64)
+        th = np.where((ts > 0) & (rng.random(n) < 0.5), rng.integers(1, 21, n), 0).astype(np.int64)
+        start = (rng.random(n) * (L - span + 1)).astype(np.int64)
+        mapq = rng.integers(0, 61, n).astype(np.uint8)
+        # CIGAR layout: [H] [S] M g M g ... M [S] [H]
+        has = lambda a: (a > 0).astype(np.int64)  # noqa: E731
+        nops = has(lh) + has(ls) + 2 * nm - 1 + has(ts) + has(th)
+        off = np.concatenate([[0], np.cumsum(nops)]).astype(np.int64)
+        cigar = np.zeros(int(off[-1]), np.uint32)
+        core = off[:-1] + has(lh) + has(ls)
+        cigar[core[rid] + 2 * within] = (mlen.astype(np.uint32) << 4) | mop.astype(np.uint32)
+        cigar[(core[rid] + 2 * within + 1)[gap]] = ((glen.astype(np.uint32) << 4) | gop.astype(np.uint32))[gap]
+        cigar[off[:-1][lh > 0]] = _cig(5, lh[lh > 0])
+        cigar[(core - 1)[ls > 0]] = _cig(4, ls[ls > 0])
+        tail = core + 2 * nm - 1
+        cigar[tail[ts > 0]] = _cig(4, ts[ts > 0])
+        cigar[(tail + has(ts))[th > 0]] = _cig(5, th[th > 0])
+        l_seq = ls + m_sum + i_sum + ts
+        if not unsorted:
+            o = np.argsort(start, kind="stable")
+            src = np.repeat(off[:-1][o], nops[o]) + (np.arange(int(off[-1])) - np.repeat(
+                np.concatenate([[0], np.cumsum(nops[o])[:-1]]), nops[o]))
+            cigar = cigar[src]
+            start, nops, mapq, ls, l_seq = start[o], nops[o], mapq[o], ls[o], l_seq[o]
+        nbytes = l_seq // 2
+        seq_off = np.concatenate([[0], np.cumsum(nbytes)]).astype(np.uint64)
+        tot = 2 * int(seq_off[-1])
+        codes = ACGT[rng.integers(0, 4, tot)]
+        if n_frac > 0:
+            codes[rng.random(tot) < n_frac] = CODE_N
+        parts.append(ReadSet(
+            references=[], lengths=[], tid=np.zeros(n, np.int32), pos=start.astype(np.int32),
+            flag=np.zeros(n, np.uint16), mapq=mapq,
+            cig_off=np.concatenate([[0], np.cumsum(nops)]).astype(np.uint64), cigar=cigar,
+            l_seq=l_seq.astype(np.int32), seq_off=seq_off, seq=((codes[0::2] << 4) | codes[1::2]).astype(np.uint8),
+            qual_off=2 * seq_off, qual=rng.integers(2, 41, tot).astype(np.uint8), qstart=ls.astype(np.int32)))
+    return concat(parts, [c[0] for c in contigs], [int(c[1]) for c in contigs])
+
+
 def make_config(name: str, unsorted: bool = False, contigs=None, reads=None) -> ReadSet:
     c = CONFIGS[name.lower()]
     if c.get("per_contig"):  # each contig's reads from its own seed (contig_reads)

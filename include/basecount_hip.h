@@ -138,6 +138,13 @@ int bc_ctx_release_scratch(bc_ctx* ctx);
  *                         only for spans > 4096)
  *   BC_SHAPE_RC           read-chunked k_rc (+ k_stats) for every sorted batch
  *   BC_SHAPE_TILE_NO_SOLO tiled k_pileup, never the sparse sweep
+ *   BC_SHAPE_OPS          scan-expanded k_ops (+ k_stats) in k_rc's place, for batches of many-op
+ *                         reads (nanopore-like: tens to thousands of CIGAR ops per read).  Never
+ *                         picked by BC_SHAPE_AUTO.  bc_count under it also takes unsorted
+ *                         BC_SEQ_EVENT batches (any sequence alignment); BC_SEQ_BAM batches keep
+ *                         k_count.  Reads no index: BC_INDEX_AUTO builds none, reads_per_block
+ *                         (0 = from the batch) is the reads per k_ops workgroup.  Timed under
+ *                         BC_K_COUNT.
  * tile_waves: 0 = from the depth, else 1, 2, 4 or 8 waves per 64-position tile (BC_E_ARG
  * otherwise).  reads_per_block: 0 = automatic, else 1..32768 reads per k_count workgroup
  * (unsorted batches).                                                                          */
@@ -145,6 +152,7 @@ int bc_ctx_release_scratch(bc_ctx* ctx);
 #define BC_SHAPE_TILE 1
 #define BC_SHAPE_RC 2
 #define BC_SHAPE_TILE_NO_SOLO 3
+#define BC_SHAPE_OPS 4
 int bc_ctx_set_shape(bc_ctx* ctx, int shape, int tile_waves, int reads_per_block);
 int bc_sync(bc_ctx* ctx);
 
