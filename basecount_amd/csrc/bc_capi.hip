@@ -298,6 +298,16 @@ int bc_ctx_set_shape(bc_ctx* c, int shape, int tile_waves, int rpb) {
     return BC_OK;
 }
 
+int bc_pileup_plan(const bc_reads* r, int64_t ref_len, int shape, int tile_waves, bc_plan* out) {
+    if (!r || !out) return fail(BC_E_ARG, "NULL argument");
+    if (r->n_reads < 0 || ref_len < 0) return fail(BC_E_ARG, "bc_pileup_plan: n_reads or ref_len < 0");
+    if (shape < BC_SHAPE_AUTO || shape > BC_SHAPE_OPS) return fail(BC_E_ARG, "unknown BC_SHAPE_* value");
+    if (tile_waves != 0 && tile_waves != 1 && tile_waves != 2 && tile_waves != 4 && tile_waves != 8)
+        return fail(BC_E_ARG, "tile_waves must be 0, 1, 2, 4 or 8");
+    bc::pileup_plan(*r, ref_len, shape, tile_waves, *out);
+    return BC_OK;
+}
+
 int bc_sync(bc_ctx* c) {
     if (!c) return fail(BC_E_ARG, "ctx is NULL");
     DeviceGuard g(c->device);

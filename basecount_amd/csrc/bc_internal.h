@@ -113,7 +113,14 @@ constexpr double kRcMinReadsPerTile = 2048.0;
 bool use_rc(const bc_reads& r, int64_t L, int shape);
 constexpr int kTileMaxSpan = 4096;  // beyond this span the tiled kernel's look-back gets too long
 // the tiled kernels: waves per 64-position tile from the depth (1 = the sparse sweep k_pileup_solo)
+// (with per_tile the mean reads a tile walks: one wave up to kSoloMaxReadsPerTile, else the
+// smallest S in {4, 8} with per_tile <= kTileReadsPerWave x S)
+constexpr double kSoloMaxReadsPerTile = 48.0;
+constexpr double kTileReadsPerWave = 512.0;
+double pileup_reads_per_tile(const bc_reads& r, int64_t L, int64_t max_end);
 int pileup_waves(const bc_reads& r, int64_t L, int64_t max_end, int tile_waves);
+// bc_pileup_plan: what bc_pileup launches for the batch's header (no pointer of r is read)
+void pileup_plan(const bc_reads& r, int64_t L, int shape, int tile_waves, bc_plan& p);
 inline bool pileup_is_solo(const bc_reads& r, int64_t L, int shape, int tile_waves) {
     return shape != BC_SHAPE_TILE_NO_SOLO && pileup_waves(r, L, r.max_end, tile_waves) == 1;
 }

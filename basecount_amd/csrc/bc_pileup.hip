@@ -70,10 +70,16 @@ __device__ __forceinline__ void tail_sums(const uint32_t (&c)[K], const OctPos& 
     oct_sums<K, NS>(c, o, ts, us, nf, nf2, h, h2);
 }
 
-// Fused kernel 2: the statistics of a tile from its reduced counts f[K][kTile] in LDS, eight
-// lanes per position (bc_stats.h: lane j < K owns column j; the position's first lane adds the
-// terms).  A wave finishes 8 positions per pass: the tile's eight 8-position groups `first`,
-// `first + step`, ... are this wave's.  Nothing is read from global memory (the log2 table is in
+// Fused kernel 2: the statistics of a tile from its reduced counts f[K][kTile] in LDS (bc_stats.h:
+// lane j of a position's lanes owns column j; the position's first lane adds the terms).  The
+// tile's four 16-position groups `first`, `first + step`, ... are this wave's.  A group whose
+// columns 4.. (deletions, N) are zero at all 16 positions (wave-uniform; every group of an all-M
+// batch) takes ONE pass with four lanes per position: the lanes own A, C, G, T, the sums run over
+// those four columns, and the zero columns' counts and percentages (0.0, or -1.0 at zero
+// coverage: oct_terms at a zero count) are stored as constants.  Any other group takes two passes
+// of 8 positions with eight lanes each.  The two layouts share one body (the lane's shift is
+// uniform): col_terms per column, the columns added in the same order (a zero count adds no
+// term), so they give the same bits.  Nothing is read from global memory (the log2 table is in
 // LDS), and a pass stores its counts, percentages, coverage and entropies last: the stores wait
 // for nothing, and nothing but the wave's next pass or tile waits for them.
 template <int K, typename ARGS>
@@ -82,29 +88,46 @@ __device__ __forceinline__ void tile_tail(const ARGS& A, lds_u32* f, lds_f64* ta
     // (the tail's lane-derived indices and addresses are computed here, not hoisted out of the
     // tile loop and kept in registers through the read walk)
     asm volatile("" : "+v"(lane));
-    const int j = lane & 7;
-    for (int q = first; q < kTile / 8; q += step) {
-        const int p = 8 * q + (lane >> 3);
-        const int64_t P = t0 + p;
-        const bool col = j < K && P < L;
-        uint32_t c[K];
+    for (int gq = first; gq < kTile / 16; gq += step) {
+        uint32_t rare = 0;
 #pragma unroll
-        for (int i = 0; i < K; ++i) c[i] = f[i * kTile + p];
-        const uint32_t cj = f[(j < K ? j : 0) * kTile + p];
-        const OctPos o = oct_pos<K>(c);
-        const ColTerms r = col_terms(o, cj, j, col, tab);
-        // batches without deletions or N: those columns' terms are zero in every lane (uniform)
-        double h, h2;
-        if (__any(col && j >= 4 && cj != 0)) tail_sums<K, K>(c, o, r.t, r.u, A.nf, A.nf2, h, h2);
-        else tail_sums<K, 4>(c, o, r.t, r.u, A.nf, A.nf2, h, h2);
-        if (col) {
-            A.counts[(int64_t)j * L + P] = (int32_t)cj;
-            if (A.pc) A.pc[(int64_t)j * L + P] = r.pct;
-        }
-        if (j == 0 && P < L) {
-            A.cov[P] = (int32_t)o.cov;
-            A.ent[P] = h;
-            A.sec[P] = h2;
+        for (int i = 4; i < K; ++i) rare |= f[i * kTile + 16 * gq + (lane & 15)];
+        const bool four = !__any(rare != 0);  // (uniform) four lanes per position, one pass
+        const int sh = four ? 2 : 3;
+        const int j = lane & ((1 << sh) - 1);
+        for (int q = 0; q < (four ? 1 : 2); ++q) {
+            const int p = 16 * gq + 8 * q + (lane >> sh);
+            const int64_t P = t0 + p;
+            const bool col = j < K && P < L;
+            uint32_t c[K];
+#pragma unroll
+            for (int i = 0; i < K; ++i) c[i] = f[i * kTile + p];
+            const uint32_t cj = f[(j < K ? j : 0) * kTile + p];
+            const OctPos o = oct_pos<K>(c);
+            const ColTerms r = col_terms(o, cj, j, col, tab);
+            double h, h2;
+            if (four) tail_sums<K, 4>(c, o, r.t, r.u, A.nf, A.nf2, h, h2);
+            else tail_sums<K, K>(c, o, r.t, r.u, A.nf, A.nf2, h, h2);
+            if (col) {
+                A.counts[(int64_t)j * L + P] = (int32_t)cj;
+                if (A.pc) A.pc[(int64_t)j * L + P] = r.pct;
+            }
+            // the zero columns, which no lane owns.  K = 6: lane j stores column 4 + j; K = 5: the
+            // first lane stores the one column with its own outputs (either form for both K costs
+            // one of the quality variants a spilled VGPR: scripts/resources.py)
+            if (K > 5 && four && j + 4 < K && P < L) {
+                A.counts[(int64_t)(j + 4) * L + P] = 0;
+                if (A.pc) A.pc[(int64_t)(j + 4) * L + P] = o.cov != 0 ? 0.0 : -1.0;
+            }
+            if (j == 0 && P < L) {
+                A.cov[P] = (int32_t)o.cov;
+                A.ent[P] = h;
+                A.sec[P] = h2;
+                if (K == 5 && four) {
+                    A.counts[(int64_t)4 * L + P] = 0;
+                    if (A.pc) A.pc[(int64_t)4 * L + P] = o.cov != 0 ? 0.0 : -1.0;
+                }
+            }
         }
     }
 }
@@ -533,13 +556,113 @@ __global__ __launch_bounds__(256, 4) void k_pileup_solo(PileArgs A) {
 
 int pileup_waves(const bc_reads& r, int64_t L, int64_t max_end, int tile_waves) {
     if (tile_waves == 1 || tile_waves == 2 || tile_waves == 4 || tile_waves == 8) return tile_waves;
-    // waves per tile from the mean number of reads a tile walks
-    // reads overlapping a tile ~ density * (span + 63); aim for ~48 reads per wave
+    // waves per tile from the mean number of reads a tile walks: up to 48 one wave (the sparse
+    // sweep), else the smallest S in {4, 8} with per_tile <= 512 S.  Sized for batches in flight:
+    // a wave holds its slot for the workgroup's whole life, so it is the resident waves that set
+    // the rate of a stream of batches.  Four 4-wave workgroups fill a CU (16 waves, 4 x 40 KiB
+    // of LDS) where two 8-wave ones wait on each other's barriers; two waves per tile (three
+    // 4-wave workgroups of two tiles per CU) were behind four at every depth measured, eight
+    // behind four up to the switch to k_rc ("What bounds C2").  One batch
+    // alone finishes sooner with tile_waves = 8.
+    const double per_tile = pileup_reads_per_tile(r, L, max_end);
+    if (per_tile <= kSoloMaxReadsPerTile) return 1;
+    return per_tile <= kTileReadsPerWave * 4 ? 4 : 8;
+}
+
+double pileup_reads_per_tile(const bc_reads& r, int64_t L, int64_t max_end) {
+    // reads overlapping a tile ~ density * (span + 63)
     const int64_t reach = max_end > L ? max_end : L;
-    const double per_tile = reach > 0 ? (double)r.n_reads * (double)(r.max_span + kTile - 1) / (double)reach : 0.0;
-    int S = 1;
-    while (S < 8 && per_tile > 48.0 * S) S *= 2;
-    return S;
+    return reach > 0 ? (double)r.n_reads * (double)(r.max_span + kTile - 1) / (double)reach : 0.0;
+}
+
+namespace {
+
+// k_pileup's launch shape for n_tiles tiles at S waves per tile
+struct TileShape {
+    int nw, groups;  // waves and tiles per workgroup
+    int64_t blocks;
+    size_t lds;      // dynamic
+};
+TileShape tile_shape(int64_t n_tiles, int S) {
+    TileShape t;
+    t.nw = S >= 4 ? S : 4;
+    t.groups = t.nw / S;
+    t.blocks = (n_tiles + t.groups - 1) / t.groups;
+    const int64_t cap = 256 * 64;
+    if (t.blocks > cap) t.blocks = cap;
+    t.blocks = (t.blocks + 7) / 8 * 8;  // a multiple of the XCD count (see the kernel's tile mapping)
+    t.lds = pileup_lds_bytes(t.nw, t.groups);
+    return t;
+}
+
+// the sparse sweep's: tiles per wave and workgroups of kSoloWaves waves (sump: whole quarter
+// buffers per wave)
+constexpr int kSoloWaves = 4;
+int64_t solo_tiles_per_wave(int64_t n_tiles, bool sump) {
+    // ~8 rounds of resident waves (256 CUs x 16): shorter runs shorten the last round's tail
+    // (C5: 31.6 ms at 2 rounds, 30.2-30.6 at 4-8, 30.4-30.8 at 16-32)
+    const int64_t target_waves = 256 * 16 * 8;
+    int64_t tpw = (n_tiles + target_waves - 1) / target_waves;
+    if (tpw < 1) tpw = 1;
+    if (sump) tpw = (tpw + 31) / 32 * 32;
+    return tpw;
+}
+int64_t solo_blocks(int64_t n_tiles, int64_t tpw) {
+    const int64_t waves = (n_tiles + tpw - 1) / tpw;
+    const int64_t blocks = (waves + kSoloWaves - 1) / kSoloWaves;
+    return (blocks + 7) / 8 * 8;  // a multiple of the XCD count (see the kernel's tile mapping)
+}
+
+// 32-bit reads, tiles and positions when they fit
+bool tiles_fit_i32(int64_t n, int64_t n_tiles, int max_span) {
+    return n < (int64_t)0x7FFFFF00 && n_tiles * kTile + max_span + 2 * kTile < (int64_t)0x7FFFFF00;
+}
+
+}  // namespace
+
+void pileup_plan(const bc_reads& r, int64_t L, int shape, int tile_waves, bc_plan& p) {
+    p = bc_plan{};
+    p.blocks_per_cu = -1;
+    p.reads_per_tile = pileup_reads_per_tile(r, L, r.max_end);
+    if (use_rc(r, L, shape)) {
+        p.kernel = BC_PLAN_RC;
+        return;
+    }
+    const int S = pileup_waves(r, L, r.max_end, tile_waves);
+    const int64_t reach = r.max_end > L ? r.max_end : L;
+    const int64_t n_tiles = (reach + kTile - 1) / kTile;
+    const bool i32 = tiles_fit_i32(r.n_reads, n_tiles, r.max_span);
+    const void* fn;
+    size_t dyn;
+    p.waves_per_tile = S;
+    if (S == 1 && shape != BC_SHAPE_TILE_NO_SOLO) {
+        p.kernel = BC_PLAN_SOLO;
+        p.block_threads = 64 * kSoloWaves;
+        p.blocks = solo_blocks(n_tiles, solo_tiles_per_wave(n_tiles, false));
+        dyn = (size_t)kSoloWaves * (kRecBytes + kStageRegion);
+        p.lds_bytes = (int32_t)dyn;
+        fn = i32 ? (const void*)k_pileup_solo<false, 5, true, false, int32_t>
+                 : (const void*)k_pileup_solo<false, 5, true, false, int64_t>;
+    } else {
+        const TileShape t = tile_shape(n_tiles, S);
+        p.kernel = BC_PLAN_TILES;
+        p.block_threads = 64 * t.nw;
+        p.blocks = t.blocks;
+        dyn = t.lds;
+        p.lds_bytes = (int32_t)(dyn + 8 * 2 * (i32 ? 4 : 8));  // + rng, the static range hand-off
+        fn = i32 ? (const void*)k_pileup<false, 5, true, int32_t> : (const void*)k_pileup<false, 5, true, int64_t>;
+    }
+    if (n_tiles == 0) p.blocks = 0;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        (void)hipGetLastError();
+        return;
+    }
+    // (more than 64 KiB of dynamic LDS must be allowed per kernel before the runtime counts with it)
+    (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024);
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, p.block_threads, dyn) == hipSuccess) p.blocks_per_cu = nb;
+    else (void)hipGetLastError();
 }
 
 hipError_t launch_pileup_tiles(hipStream_t s, const bc_reads& r, int64_t L, int64_t max_end, uint32_t mbq, int k,
@@ -566,16 +689,12 @@ hipError_t launch_pileup_tiles(hipStream_t s, const bc_reads& r, int64_t L, int6
     A.S = S;
     if (parts) parts->fused = false;
     if (S == 1 && shape != BC_SHAPE_TILE_NO_SOLO) {
-        // sparse: waves sweep contiguous tile runs; ~8 rounds of resident waves (256 CUs x 16): shorter
-        // runs shorten the last round's tail (C5: 31.6 ms at 2 rounds, 30.2-30.6 at 4-8, 30.4-30.8 at 16-32)
-        const int nw = 4;
-        const int64_t target_waves = 256 * 16 * 8;
-        A.tiles_per_wave = (A.n_tiles + target_waves - 1) / target_waves;
-        if (A.tiles_per_wave < 1) A.tiles_per_wave = 1;
+        // sparse: waves sweep contiguous tile runs
+        const int nw = kSoloWaves;
         const bool sump = parts && stats && L >= kNpBuf;
         const bool nostore = sump && parts->no_store;
+        A.tiles_per_wave = solo_tiles_per_wave(A.n_tiles, sump);
         if (sump) {  // whole quarter buffers per wave: the summary partials come for free
-            A.tiles_per_wave = (A.tiles_per_wave + 31) / 32 * 32;
             A.sub_ent = parts->sub_ent;
             A.sub_cov = parts->sub_cov;
             A.sub_nz = parts->sub_nz;
@@ -585,13 +704,11 @@ hipError_t launch_pileup_tiles(hipStream_t s, const bc_reads& r, int64_t L, int6
             A.cov_tail = parts->cov_tail;
             A.ent_tail = parts->ent_tail;
         }
-        const int64_t waves = (A.n_tiles + A.tiles_per_wave - 1) / A.tiles_per_wave;
-        int64_t blocks = (waves + nw - 1) / nw;
-        blocks = (blocks + 7) / 8 * 8;  // a multiple of the XCD count (see the kernel's tile mapping)
+        const int64_t blocks = solo_blocks(A.n_tiles, A.tiles_per_wave);
         const dim3 grid((unsigned)blocks), block(64 * nw);
         const size_t lds = (size_t)nw * (kRecBytes + kStageRegion) + (sump ? (size_t)nw * kLeafDoubles * 8 : 0);
         // 32-bit reads and positions when they fit (the cursor loop then stays on the scalar unit)
-        const bool i32 = A.n < (int64_t)0x7FFFFF00 && A.n_tiles * kTile + A.max_span + 2 * kTile < (int64_t)0x7FFFFF00;
+        const bool i32 = tiles_fit_i32(A.n, A.n_tiles, A.max_span);
 #define BC_SOLO(Q, KK, ST)                                                                                       \
     do {                                                                                                         \
         if (nostore && i32)                                                                                      \
@@ -618,14 +735,11 @@ hipError_t launch_pileup_tiles(hipStream_t s, const bc_reads& r, int64_t L, int6
 #undef BC_SOLO
         return hipGetLastError();
     }
-    const int nw = S >= 4 ? S : 4;
-    const int groups = nw / S;
-    int64_t blocks = (A.n_tiles + groups - 1) / groups;
-    const int64_t cap = 256 * 64;
-    if (blocks > cap) blocks = cap;
-    blocks = (blocks + 7) / 8 * 8;  // a multiple of the XCD count (see the kernel's tile mapping)
+    const TileShape ts = tile_shape(A.n_tiles, S);
+    const int nw = ts.nw;
+    const int64_t blocks = ts.blocks;
     const dim3 grid((unsigned)blocks), block(64 * nw);
-    const size_t lds = pileup_lds_bytes(nw, groups);
+    const size_t lds = ts.lds;
     if (stats && accumulate) return hipErrorInvalidValue;  // no caller: the fused tail only stores
     // diagnostic only: BC_TRACE=<file> dumps the per-wave phase stamps of the 20th launch
     static unsigned long long* tbuf = nullptr;
@@ -640,8 +754,7 @@ hipError_t launch_pileup_tiles(hipStream_t s, const bc_reads& r, int64_t L, int6
         if (!tbuf && hipMallocManaged((void**)&tbuf, 8 * (size_t)256 * 64 * 16 * kTracePhases) != hipSuccess) tbuf = nullptr;
         if (tn <= (size_t)256 * 64 * 16 * kTracePhases) A.trace = tbuf;
     }
-    // 32-bit reads, tiles and positions when they fit
-    const bool i32 = A.n < (int64_t)0x7FFFFF00 && A.n_tiles * kTile + A.max_span + 2 * kTile < (int64_t)0x7FFFFF00;
+    const bool i32 = tiles_fit_i32(A.n, A.n_tiles, A.max_span);
     const TileArgs T = A;  // k_pileup takes the walk's fields only
     // > 64 KiB of dynamic LDS must be allowed per kernel (160 KiB per CU on gfx950)
 #define BC_PILE(Q, KK, ST)                                                                                   \

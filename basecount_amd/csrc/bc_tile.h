@@ -310,9 +310,15 @@ constexpr int kLog2TabBytes = 64 * 4 * 8;  // log2d::kTab
 
 // dynamic LDS of k_pileup: [rec: nw x 3 KB][stage: nw x kStageRegion][fin: groups x 1.5 KB]
 // [the log2 table: 2 KB].  fin[g] collects the counts of group g's tile (LDS atomics) and is what
-// the statistics tail reads.  Two 8-wave blocks fit a CU's 160 KiB.
+// the statistics tail reads.  Two 8-wave blocks fit a CU's 160 KiB, and four 4-wave blocks of
+// one tile (with k_pileup's static range hand-off, 64 B at 32-bit indices) when each is rounded
+// up to the 1,280 B the LDS is allocated in: 4 x 40,960 B are the 160 KiB exactly.
 constexpr int kRecBytes = kTile * 3 * 16;
+constexpr int kLdsGranule = 1280;
 static_assert(2 * (8 * (kRecBytes + kStageRegion) + kFinBytes + kLog2TabBytes) <= 160 * 1024, "2 blocks per CU");
+static_assert(4 * ((4 * (kRecBytes + kStageRegion) + kFinBytes + kLog2TabBytes + 64 + kLdsGranule - 1) / kLdsGranule *
+                   kLdsGranule) <= 160 * 1024,
+              "4 four-wave blocks per CU");
 __host__ __device__ inline size_t pileup_lds_bytes(int nw, int groups) {
     return (size_t)nw * (kRecBytes + kStageRegion) + (size_t)groups * kFinBytes + kLog2TabBytes;
 }

@@ -48,6 +48,22 @@ class BcReads(C.Structure):
     ]
 
 
+class BcPlan(C.Structure):
+    _fields_ = [
+        ("kernel", C.c_int32),  # BC_PLAN_RC 0 / BC_PLAN_SOLO 1 / BC_PLAN_TILES 2
+        ("waves_per_tile", C.c_int32),
+        ("block_threads", C.c_int32),
+        ("lds_bytes", C.c_int32),
+        ("blocks", C.c_int64),
+        ("blocks_per_cu", C.c_int32),  # -1: no device to ask
+        ("reserved", C.c_int32),
+        ("reads_per_tile", C.c_double),
+    ]
+
+
+PLAN_KERNELS = ("rc", "solo", "tiles")  # BC_PLAN_*
+
+
 class BcError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(msg)
@@ -71,6 +87,7 @@ def lib() -> C.CDLL:
         "bc_ctx_stream": ([vp, C.POINTER(vp)], C.c_int),
         "bc_sync": ([vp], C.c_int),
         "bc_ctx_set_shape": ([vp, C.c_int, C.c_int, C.c_int], C.c_int),
+        "bc_pileup_plan": ([C.POINTER(BcReads), i64, C.c_int, C.c_int, C.POINTER(BcPlan)], C.c_int),
         "bc_malloc": ([vp, C.c_size_t, C.POINTER(vp)], C.c_int),
         "bc_free": ([vp, vp], C.c_int),
         "bc_memcpy_h2d": ([vp, vp, vp, C.c_size_t], C.c_int),
@@ -148,6 +165,25 @@ def device_count() -> int:
     n = C.c_int(0)
     check(lib().bc_device_count(C.byref(n)))
     return n.value
+
+
+def pileup_plan(reads, L: int, shape: str = "auto", tile_waves: int = 0) -> dict:
+    """bc_pileup_plan: what bc_pileup would launch for a sorted batch on a reference of L
+    positions under (shape, tile_waves).  ``reads``: a DeviceReads, a BcReads, or a dict with
+    n_reads, max_span and max_end (only the header is read, never a pointer).  Returns kernel
+    ("rc", "solo" or "tiles"), waves_per_tile, block_threads, lds_bytes, blocks, reads_per_tile
+    and blocks_per_cu (the workgroups resident per CU; -1 without a device)."""
+    if isinstance(reads, dict):
+        r = BcReads()
+        r.n_reads, r.max_span, r.max_end = int(reads["n_reads"]), int(reads["max_span"]), int(reads["max_end"])
+        r.sorted, r.seq_layout = 1, BC_SEQ_EVENT
+    else:
+        r = reads.r if isinstance(reads, DeviceReads) else reads
+    p = BcPlan()
+    check(lib().bc_pileup_plan(C.byref(r), int(L), SHAPES[shape], int(tile_waves), C.byref(p)))
+    return {"kernel": PLAN_KERNELS[p.kernel], "waves_per_tile": p.waves_per_tile, "block_threads": p.block_threads,
+            "lds_bytes": p.lds_bytes, "blocks": p.blocks, "blocks_per_cu": p.blocks_per_cu,
+            "reads_per_tile": p.reads_per_tile}
 
 
 class DeviceBuffer:

@@ -154,6 +154,43 @@ int bc_ctx_release_scratch(bc_ctx* ctx);
 #define BC_SHAPE_TILE_NO_SOLO 3
 #define BC_SHAPE_OPS 4
 int bc_ctx_set_shape(bc_ctx* ctx, int shape, int tile_waves, int reads_per_block);
+
+/* What bc_pileup launches for a coordinate-sorted BC_SEQ_EVENT batch on a reference of ref_len
+ * positions under (shape, tile_waves), from the batch's header alone: n_reads, max_span and
+ * max_end are read, no pointer is dereferenced, nothing is enqueued and no context is needed.
+ * With reads_per_tile = n_reads x (max_span + 63) / max(ref_len, max_end), BC_SHAPE_AUTO takes
+ *   reads_per_tile <= 48      the sparse sweep k_pileup_solo, one wave per 64-position tile;
+ *   below 2,048               the tiled k_pileup with FOUR waves per tile: sized for batches in
+ *                             flight (four such workgroups are resident per CU; a stream of
+ *                             C2-sized batches runs ~20 % faster than with eight per tile);
+ *   from 2,048 on             the read-chunked k_rc (+ k_stats).
+ * BC_SHAPE_TILE / _NO_SOLO keep the tiled kernel beyond 2,048, with eight waves per tile there.
+ * tile_waves = 8 remains for a caller that wants ONE batch's latency: a single C2-sized launch
+ * takes ~15.8 us with eight waves per tile and ~18.5 us with four.
+ *   kernel          BC_PLAN_RC (the fields below are then 0), BC_PLAN_SOLO or BC_PLAN_TILES
+ *   waves_per_tile  1, 2, 4 or 8
+ *   block_threads   threads per workgroup
+ *   lds_bytes       LDS per workgroup, dynamic + static (bc_pileup's launch; the sparse sweep
+ *                   with summary partials asks for 2,560 B more)
+ *   blocks          workgroups of the launch
+ *   blocks_per_cu   workgroups resident per CU as the HIP runtime counts them for the mbq = 0,
+ *                   k = 5 variant (hipOccupancyMaxActiveBlocksPerMultiprocessor); -1 when no
+ *                   device is visible
+ *   reads_per_tile  the figure above                                                          */
+#define BC_PLAN_RC 0
+#define BC_PLAN_SOLO 1
+#define BC_PLAN_TILES 2
+typedef struct bc_plan {
+    int32_t kernel;
+    int32_t waves_per_tile;
+    int32_t block_threads;
+    int32_t lds_bytes;
+    int64_t blocks;
+    int32_t blocks_per_cu;
+    int32_t reserved;
+    double reads_per_tile;
+} bc_plan;
+int bc_pileup_plan(const bc_reads* reads, int64_t ref_len, int shape, int tile_waves, bc_plan* out);
 int bc_sync(bc_ctx* ctx);
 
 /* Library-owned device memory helpers (for hosts without another allocator). */
