@@ -638,7 +638,8 @@ void pileup_plan(const bc_reads& r, int64_t L, int shape, int tile_waves, bc_pla
     if (S == 1 && shape != BC_SHAPE_TILE_NO_SOLO) {
         p.kernel = BC_PLAN_SOLO;
         p.block_threads = 64 * kSoloWaves;
-        p.blocks = solo_blocks(n_tiles, solo_tiles_per_wave(n_tiles, false));
+        p.tiles_per_wave = (int32_t)solo_tiles_per_wave(n_tiles, false);
+        p.blocks = solo_blocks(n_tiles, p.tiles_per_wave);
         dyn = (size_t)kSoloWaves * (kRecBytes + kStageRegion);
         p.lds_bytes = (int32_t)dyn;
         fn = i32 ? (const void*)k_pileup_solo<false, 5, true, false, int32_t>

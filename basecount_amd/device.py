@@ -56,7 +56,7 @@ class BcPlan(C.Structure):
         ("lds_bytes", C.c_int32),
         ("blocks", C.c_int64),
         ("blocks_per_cu", C.c_int32),  # -1: no device to ask
-        ("reserved", C.c_int32),
+        ("tiles_per_wave", C.c_int32),  # BC_PLAN_SOLO: tiles per wave of bc_pileup's sweep; else 0
         ("reads_per_tile", C.c_double),
     ]
 
@@ -171,8 +171,10 @@ def pileup_plan(reads, L: int, shape: str = "auto", tile_waves: int = 0) -> dict
     """bc_pileup_plan: what bc_pileup would launch for a sorted batch on a reference of L
     positions under (shape, tile_waves).  ``reads``: a DeviceReads, a BcReads, or a dict with
     n_reads, max_span and max_end (only the header is read, never a pointer).  Returns kernel
-    ("rc", "solo" or "tiles"), waves_per_tile, block_threads, lds_bytes, blocks, reads_per_tile
-    and blocks_per_cu (the workgroups resident per CU; -1 without a device)."""
+    ("rc", "solo" or "tiles"), waves_per_tile, block_threads, lds_bytes, blocks, reads_per_tile,
+    blocks_per_cu (the workgroups resident per CU; -1 without a device) and tiles_per_wave (the
+    sparse sweep's run of tiles per wave in bc_pileup; the fused-summary calls round it up to a
+    multiple of 32; 0 for the other kernels)."""
     if isinstance(reads, dict):
         r = BcReads()
         r.n_reads, r.max_span, r.max_end = int(reads["n_reads"]), int(reads["max_span"]), int(reads["max_end"])
@@ -183,7 +185,7 @@ def pileup_plan(reads, L: int, shape: str = "auto", tile_waves: int = 0) -> dict
     check(lib().bc_pileup_plan(C.byref(r), int(L), SHAPES[shape], int(tile_waves), C.byref(p)))
     return {"kernel": PLAN_KERNELS[p.kernel], "waves_per_tile": p.waves_per_tile, "block_threads": p.block_threads,
             "lds_bytes": p.lds_bytes, "blocks": p.blocks, "blocks_per_cu": p.blocks_per_cu,
-            "reads_per_tile": p.reads_per_tile}
+            "tiles_per_wave": p.tiles_per_wave, "reads_per_tile": p.reads_per_tile}
 
 
 class DeviceBuffer:

@@ -176,6 +176,11 @@ int bc_ctx_set_shape(bc_ctx* ctx, int shape, int tile_waves, int reads_per_block
  *   blocks_per_cu   workgroups resident per CU as the HIP runtime counts them for the mbq = 0,
  *                   k = 5 variant (hipOccupancyMaxActiveBlocksPerMultiprocessor); -1 when no
  *                   device is visible
+ *   tiles_per_wave  BC_PLAN_SOLO: the consecutive tiles one wave of bc_pileup's (and bc_count's)
+ *                   sweep takes, 1 up to 2^21 positions and ceil(tiles / 32,768) beyond; the
+ *                   fused-summary calls (bc_pileup_summary / bc_pileup_partials on a reference
+ *                   of 8,192 positions or more) round it up to a multiple of 32, a whole
+ *                   quarter of a summary buffer.  0 for the other kernels
  *   reads_per_tile  the figure above                                                          */
 #define BC_PLAN_RC 0
 #define BC_PLAN_SOLO 1
@@ -187,7 +192,7 @@ typedef struct bc_plan {
     int32_t lds_bytes;
     int64_t blocks;
     int32_t blocks_per_cu;
-    int32_t reserved;
+    int32_t tiles_per_wave;
     double reads_per_tile;
 } bc_plan;
 int bc_pileup_plan(const bc_reads* reads, int64_t ref_len, int shape, int tile_waves, bc_plan* out);

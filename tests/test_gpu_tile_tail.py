@@ -187,23 +187,31 @@ def test_tail_all_m_batch(ctx, k):
     check(got, (cnt[:, :k].T.astype(np.int32),) + tuple(O.stats(cnt, k == 6)), ("all-M", k))
 
 
-def test_tail_more_than_one_tile_per_block(ctx):
-    """More tiles than the grid has blocks: the blocks of tiles 0-2 go on to the last three
-    tiles, so fin and rng are reused behind the loop-end barrier.  Reads at both ends."""
-    L = 64 * 16_384 + 130
+@pytest.mark.parametrize("waves,rounds", [(8, 16_384), (4, 16_384), (2, 2 * 16_384), (1, 4 * 16_384)])
+def test_tail_more_than_one_tile_per_block(ctx, waves, rounds):
+    """More tiles than the grid has blocks (16,384 at the most, each of nw / S tiles), at every
+    group size: the blocks of the first tiles go on to the last three tiles, so fin and rng are
+    reused behind the loop-end barrier.  Reads at both ends."""
+    L = 64 * rounds + 130
     rng = np.random.default_rng(8)
-    reads = random_reads(rng, 1_500, 0, 192) + random_reads(rng, 1_000, 64 * 16_384 - 100, 64 * 16_384 + 64)
+    reads = random_reads(rng, 1_500, 0, 192) + random_reads(rng, 1_000, 64 * rounds - 100, 64 * rounds + 64)
     reads += random_reads(rng, 500, L - 66, L)
     b = build_batch(reads)
     cnt, (bad, _) = O.bcount(L, 0, b)
     assert bad == -1
     exp = (cnt[:, :5].T.astype(np.int32),) + tuple(O.stats(cnt, False))
-    set_waves(ctx, 8)
+    set_waves(ctx, waves)
+    r = D.DeviceReads(ctx, b)
+    p = D.pileup_plan(r, L, *ctx.shape_args[:2])
+    r.free()
+    n_tiles, groups = -(-L // 64), p["block_threads"] // 64 // waves  # tiles; tiles per block
+    assert p["kernel"] == "tiles" and p["waves_per_tile"] == waves and groups >= 1
+    assert p["blocks"] < n_tiles / groups  # some block takes a second round of tiles
     got, bad = run_pileup(ctx, b, L, 0, 5)
     assert bad == -1
-    empty = rng.integers(200, 64 * 16_384 - 200, 4_096)
+    empty = rng.integers(200, 64 * rounds - 200, 4_096)
     assert not exp[1][empty].any()
-    for sl in (slice(0, 256), slice(64 * 16_384 - 128, L), empty):
+    for sl in (slice(0, 256), slice(64 * rounds - 128, L), empty):
         check(got, exp, "multi-tile", sl)
     assert np.array_equal(got[1], exp[1])  # coverage everywhere
 

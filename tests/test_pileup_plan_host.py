@@ -109,6 +109,30 @@ def test_four_four_wave_blocks_fit_a_cu():
     assert four == 40_576 + 64 and eight == 77_568 + 64  # dynamic + the static range hand-off
 
 
+def test_tiles_per_wave_of_the_sparse_sweep():
+    """tiles_per_wave is bc_pileup's sweep run: one tile per wave up to 32,768 tiles (2^21
+    positions), then ceil(tiles / 32,768); the furthest read end counts as in the reach; 0 for the
+    tiled and the read-chunked plans."""
+    for tiles, want in ((1, 1), (2, 1), (32_767, 1), (32_768, 1), (32_769, 2), (65_536, 2), (65_537, 3),
+                        (98_304, 3), (98_305, 4), (98_306, 4), (131_072, 4), (131_073, 5)):
+        for length in (64 * (tiles - 1) + 1, 64 * tiles):  # the first and the last length of that many tiles
+            # (a reference of a tile or two is "deep" with any read on it: the sweep forced there)
+            p = plan(100, length=length) if tiles > 2 else plan(1, "tile", 1, length=length)
+            assert (p["kernel"], p["waves_per_tile"], p["tiles_per_wave"]) == ("solo", 1, want), (tiles, length)
+            assert p["blocks"] == 8 * ceil_div(ceil_div(ceil_div(tiles, want), 4), 8)
+    # the two rows-mode references of test_gpu_solo_sweep.py
+    assert plan(5_500, length=2**21 + 101, span=4_096)["tiles_per_wave"] == 2
+    assert plan(5_500, length=3 * 2**21 + 101, span=4_096)["tiles_per_wave"] == 4
+    # edge tiles past the reference end are swept too
+    p = D.pileup_plan({"n_reads": 100, "max_span": SPAN, "max_end": 2**21 + 1}, 2**21)
+    assert (p["kernel"], p["tiles_per_wave"]) == ("solo", 2)
+    p = plan(100, "tile", 1, length=2**22 + 1)
+    assert (p["kernel"], p["tiles_per_wave"]) == ("solo", 3)
+    for p in (plan(480, "tile_no_solo"), plan(481), plan(5_000, "tile", 4), plan(100, "tile_no_solo", 1, length=2**22),
+              plan(20_480), plan(100, "rc"), plan(100, "rc", length=2**22)):
+        assert p["kernel"] in ("tiles", "rc") and p["tiles_per_wave"] == 0, p
+
+
 def test_bad_arguments():
     with pytest.raises(D.BcError):
         plan(100, "tile", 3)
