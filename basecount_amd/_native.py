@@ -126,6 +126,9 @@ def bcio() -> C.CDLL:
     lib.bcio_stream_ref_len.argtypes = [C.c_void_p, C.c_int32]
     lib.bcio_stream_ref_len.restype = C.c_int64
     lib.bcio_stream_close.argtypes = [C.c_void_p]
+    lib.bcio_stream_set_inflater.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.bcio_inflate_blocks.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_int64, C.c_void_p, C.c_uint64, C.c_int]
+    lib.bcio_stream_inflate_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.bcio_stream_close.restype = None
     lib.bcio_find_ref_start.argtypes = [C.c_char_p, C.c_int32, C.POINTER(C.c_uint64)]
     lib.bcio_find_record.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.POINTER(C.c_uint64)]

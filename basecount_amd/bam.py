@@ -199,9 +199,14 @@ class BamStream:
                 ...
     """
 
-    def __init__(self, path: str, nthreads: int = 0, *, voff_range: tuple | None = None):
+    def __init__(self, path: str, nthreads: int = 0, *, voff_range: tuple | None = None, device_inflate=None,
+                 inflater: tuple | None = None):
         """``voff_range=(begin, end)``: only the records in [begin, end) (BAM virtual offsets,
-        ``find_ref_start``; end None: to the end of the file, begin None: no records)."""
+        ``find_ref_start``; end None: to the end of the file, begin None: no records).
+        ``device_inflate``: a ``device.Context`` whose GPU inflates the stream's BGZF blocks
+        (``bc_bgzf_inflate_host`` is handed to the stream as its inflater: no Python on that path;
+        a block the device refuses is inflated on the host, so errors are the host's).
+        ``inflater=(fn, user)``: any ``bcio_inflate_fn`` address (or ctypes callback) instead."""
         lib = N.bcio()
         h = C.c_void_p()
         if voff_range is None:
@@ -215,6 +220,14 @@ class BamStream:
             raise FileNotFoundError(lib.bcio_last_error().decode())
         N.bcio_check(rc)
         self._h = h
+        if device_inflate is not None:
+            inflater = device_inflate.inflater()
+        self._inflater = inflater  # keeps a ctypes callback (and the context) alive with the stream
+        self._inflate_ctx = device_inflate
+        if inflater is not None:
+            fn, user = inflater
+            N.bcio_check(lib.bcio_stream_set_inflater(h, C.cast(fn, C.c_void_p), user))
+        self.open_stats = self.inflate_stats()  # the blocks the open itself inflated (the header's)
         nr = lib.bcio_stream_n_refs(h)
         self.references = tuple(lib.bcio_stream_ref_name(h, i).decode() for i in range(nr))
         self.lengths = tuple(int(lib.bcio_stream_ref_len(h, i)) for i in range(nr))
@@ -227,6 +240,14 @@ class BamStream:
         if not out.value:
             return None
         return BamFile(None, _handle=out, _first=first)
+
+    def inflate_stats(self) -> dict:
+        """BGZF blocks inflated so far by the stream's inflater ("callback") and on the host."""
+        cb, host = C.c_int64(0), C.c_int64(0)
+        if not getattr(self, "_h", None):  # closed: nothing to add
+            return {"callback": 0, "host": 0}
+        N.bcio_check(N.bcio().bcio_stream_inflate_stats(self._h, C.byref(cb), C.byref(host)))
+        return {"callback": cb.value, "host": host.value}
 
     def batches(self, max_records: int):
         """Yield the batches; each is closed when the next one is requested."""

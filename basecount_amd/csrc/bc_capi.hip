@@ -241,6 +241,10 @@ int bc_ctx_destroy(bc_ctx* c) {
     if (c->rc_scratch) (void)hipFree(c->rc_scratch);
     if (c->out_scratch) (void)hipFree(c->out_scratch);
     if (c->sum_scratch) (void)hipFree(c->sum_scratch);
+    for (void* p : c->z_buf)
+        if (p) (void)hipFree(p);
+    for (auto& e : c->z_ev)
+        if (e) (void)hipEventDestroy(e);
     if (c->h_err) (void)hipHostFree(c->h_err);
     for (auto& v : c->ev)
         for (auto& pr : v) {
@@ -258,7 +262,9 @@ int bc_ctx_destroy(bc_ctx* c) {
 int bc_ctx_release_scratch(bc_ctx* c) {
     if (!c) return fail(BC_E_ARG, "ctx is NULL");
     DeviceGuard g(c->device);
-    if (c->rc_scratch || c->out_scratch || c->sum_scratch) HIP_TRY(hipStreamSynchronize(c->stream));
+    std::lock_guard<std::mutex> zlock(c->z_mutex);
+    if (c->rc_scratch || c->out_scratch || c->sum_scratch || c->z_buf[0] || c->z_buf[1] || c->z_buf[2] || c->z_buf[3])
+        HIP_TRY(hipStreamSynchronize(c->stream));
     // one buffer at a time: its pointer and size are cleared whether or not its free succeeded,
     // so no later call frees it twice; the first error is returned after all three
     hipError_t first = hipSuccess;
@@ -276,7 +282,131 @@ int bc_ctx_release_scratch(bc_ctx* c) {
     c->rc_scratch = nullptr;
     drop(c->out_scratch, c->out_scratch_bytes, "hipFree(out_scratch)");
     drop(c->sum_scratch, c->sum_scratch_bytes, "hipFree(sum_scratch)");
+    for (int i = 0; i < 4; ++i) drop(c->z_buf[i], c->z_bytes[i], "hipFree(inflate scratch)");
     if (first != hipSuccess) return hip_fail(first, where);
+    return BC_OK;
+}
+
+// ---- BGZF inflate (bc_inflate.hip) ----
+static_assert(sizeof(bc_zblock) == 24, "bc_zblock is 24 bytes (bcio_zblock has the same layout)");
+
+int bc_bgzf_inflate(bc_ctx* c, const uint8_t* d_comp, uint64_t comp_bytes, const bc_zblock* d_blocks, int64_t n,
+                    uint8_t* d_out, uint64_t out_bytes, uint8_t* d_status) {
+    if (!c) return fail(BC_E_ARG, "ctx is NULL");
+    if (n < 0 || n >= ((int64_t)1 << 31)) return fail(BC_E_ARG, "bc_bgzf_inflate: n must be 0 .. 2^31 - 1");
+    if (!d_comp || !d_blocks || !d_out || !d_status) return fail(BC_E_ARG, "bc_bgzf_inflate: NULL pointer");
+    if (n == 0) return BC_OK;
+    DeviceGuard g(c->device);
+    HIP_TRY(bc::launch_inflate(c->stream, d_comp, comp_bytes, d_blocks, n, d_out, out_bytes, d_status));
+    return BC_OK;
+}
+
+// grow-only device buffer i of the inflate scratch (the stream is idle between slices)
+static int z_reserve(bc_ctx* c, int i, size_t need) {
+    if (c->z_bytes[i] >= need) return BC_OK;
+    if (c->z_buf[i]) {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        HIP_TRY(hipFree(c->z_buf[i]));
+        c->z_buf[i] = nullptr;
+        c->z_bytes[i] = 0;
+    }
+    const size_t cap = need + need / 4 + 256;
+    HIP_TRY(hipMalloc(&c->z_buf[i], cap));
+    c->z_bytes[i] = cap;
+    return BC_OK;
+}
+
+int bc_bgzf_inflate_host(void* ctx, const uint8_t* h_comp, uint64_t comp_bytes, const bc_zblock* h_blocks, int64_t n,
+                         uint8_t* h_out, uint64_t out_bytes, uint8_t* h_status) {
+    bc_ctx* c = static_cast<bc_ctx*>(ctx);
+    if (!c) return fail(BC_E_ARG, "ctx is NULL");
+    if (n < 0) return fail(BC_E_ARG, "bc_bgzf_inflate_host: n < 0");
+    if (!h_comp || !h_blocks || !h_out || !h_status) return fail(BC_E_ARG, "bc_bgzf_inflate_host: NULL pointer");
+    if (n == 0) return BC_OK;
+    std::lock_guard<std::mutex> lock(c->z_mutex);
+    DeviceGuard g(c->device);
+    for (auto& e : c->z_ev)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    // slices of bounded inflated size: a fill may ask for gigabytes.  One wave per block and the
+    // kernel is latency-bound per wave, so a slice must hold at least the 8192 blocks (512 MiB) a
+    // 256-CU device keeps resident, or the slices' kernels run one after the other part-empty
+    constexpr uint64_t kSliceBytes = 512ull << 20;
+    constexpr int64_t kSliceBlocks = 1 << 16;
+    std::vector<bc_zblock> dev;
+    for (int64_t b0 = 0; b0 < n;) {
+        // the slice's blocks, those the host can already refuse left out; device offsets: the
+        // compressed span [cmin, cmax) as it lies in the file, the output packed densely
+        dev.clear();
+        uint64_t cmin = UINT64_MAX, cmax = 0, dense = 0;
+        int64_t b1 = b0;
+        for (; b1 < n && b1 - b0 < kSliceBlocks && dense < kSliceBytes; ++b1) {
+            const bc_zblock& z = h_blocks[b1];
+            bc_zblock d = z;
+            if (z.isize > 65536u || z.coff > comp_bytes || z.clen > comp_bytes - z.coff || z.uoff > out_bytes ||
+                z.isize > out_bytes - z.uoff) {
+                d.coff = UINT64_MAX;  // refused by the kernel's own check as well (status BC_Z_DESC)
+                d.clen = 0;
+                d.isize = 0;  // takes no room in the slice
+            } else {
+                cmin = std::min(cmin, z.coff);
+                cmax = std::max(cmax, z.coff + z.clen);
+            }
+            d.uoff = dense;
+            dense += d.isize;
+            dev.push_back(d);
+        }
+        const int64_t m = b1 - b0;
+        if (cmin > cmax) cmin = cmax = 0;
+        for (auto& d : dev)
+            if (d.coff != UINT64_MAX) d.coff -= cmin;
+        const uint64_t span = cmax - cmin;
+        int rc;
+        if ((rc = z_reserve(c, 0, span + 16)) != BC_OK || (rc = z_reserve(c, 1, (size_t)m * sizeof(bc_zblock))) != BC_OK ||
+            (rc = z_reserve(c, 2, dense + 16)) != BC_OK || (rc = z_reserve(c, 3, (size_t)m)) != BC_OK)
+            return rc;
+        uint8_t* d_comp = static_cast<uint8_t*>(c->z_buf[0]);
+        bc_zblock* d_blocks = static_cast<bc_zblock*>(c->z_buf[1]);
+        uint8_t* d_out = static_cast<uint8_t*>(c->z_buf[2]);
+        uint8_t* d_status = static_cast<uint8_t*>(c->z_buf[3]);
+        HIP_TRY(hipEventRecord(c->z_ev[0], c->stream));
+        if (span) HIP_TRY(hipMemcpyAsync(d_comp, h_comp + cmin, span, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_blocks, dev.data(), (size_t)m * sizeof(bc_zblock), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipEventRecord(c->z_ev[1], c->stream));
+        HIP_TRY(bc::launch_inflate(c->stream, d_comp, span, d_blocks, m, d_out, dense, d_status));
+        HIP_TRY(hipEventRecord(c->z_ev[2], c->stream));
+        HIP_TRY(hipMemcpyAsync(h_status + b0, d_status, (size_t)m, hipMemcpyDeviceToHost, c->stream));
+        // each run of blocks that lie back to back in h_out comes down as one copy
+        for (int64_t i = 0; i < m;) {
+            int64_t j = i;
+            uint64_t bytes = 0;
+            while (j < m && dev[j].coff != UINT64_MAX &&
+                   h_blocks[b0 + j].uoff == h_blocks[b0 + i].uoff + bytes) {
+                bytes += dev[j].isize;
+                ++j;
+            }
+            if (bytes)
+                HIP_TRY(hipMemcpyAsync(h_out + h_blocks[b0 + i].uoff, d_out + dev[i].uoff, bytes, hipMemcpyDeviceToHost,
+                                       c->stream));
+            i = j > i ? j : i + 1;
+        }
+        HIP_TRY(hipEventRecord(c->z_ev[3], c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        for (int k = 0; k < 3; ++k) {
+            float ms = 0.f;
+            if (hipEventElapsedTime(&ms, c->z_ev[k], c->z_ev[k + 1]) == hipSuccess) c->z_ms[k] += ms;
+        }
+        c->z_blocks += m;
+        b0 = b1;
+    }
+    return BC_OK;
+}
+
+int bc_bgzf_inflate_host_times(bc_ctx* c, double* ms, int64_t* blocks) {
+    if (!c) return fail(BC_E_ARG, "ctx is NULL");
+    std::lock_guard<std::mutex> lock(c->z_mutex);
+    if (ms)
+        for (int k = 0; k < 3; ++k) ms[k] = c->z_ms[k];
+    if (blocks) *blocks = c->z_blocks;
     return BC_OK;
 }
 

@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstdlib>
+#include <mutex>
 #include <string>
 #include <utility>
 #include <vector>
@@ -27,6 +28,13 @@ struct bc_ctx {
     size_t out_scratch_bytes = 0;
     void* sum_scratch = nullptr;           // the read-parallel summary's leaf arrays, kept zeroed
     size_t sum_scratch_bytes = 0;
+    // bc_bgzf_inflate_host: device buffers of one slice, its event pairs and the times so far
+    std::mutex z_mutex;
+    void* z_buf[4] = {};  // compressed bytes, descriptors, inflated bytes, statuses
+    size_t z_bytes[4] = {};
+    hipEvent_t z_ev[4] = {};
+    double z_ms[3] = {};
+    int64_t z_blocks = 0;
     // kernel-shape overrides (bc_ctx_set_shape); 0 = chosen from the batch
     int shape = BC_SHAPE_AUTO;
     int tile_waves = 0;
@@ -188,5 +196,10 @@ hipError_t launch_seg_vpos(hipStream_t s, const int32_t* pos, int64_t n, const i
 // bc_summary's 4 doubles of every segment's slice [voff[i], voff[i] + ref_len[i]) into out[i][4]
 hipError_t launch_sum_segments(hipStream_t s, int n_seg, const int64_t* ref_len, const int64_t* voff,
                                const int32_t* cov, const double* ent, double* out);
+
+
+// ---- BGZF inflate (bc_inflate.hip): one wave per block, every descriptor checked on the device ----
+hipError_t launch_inflate(hipStream_t s, const uint8_t* comp, uint64_t comp_bytes, const bc_zblock* blocks, int64_t n,
+                          uint8_t* out, uint64_t out_bytes, uint8_t* status);
 
 }  // namespace bc

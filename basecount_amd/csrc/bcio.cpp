@@ -828,6 +828,10 @@ struct bcio_stream {
     // range streams (bcio_stream_open_range): blocks are scanned below cend only, and the block at
     // tail_block (if any) keeps its first tail_keep inflated bytes
     uint64_t cend = UINT64_MAX, tail_block = UINT64_MAX, tail_keep = 0;
+    // bcio_stream_set_inflater: the fills' blocks go to fn first (NULL: host only)
+    bcio_inflate_fn inflater = nullptr;
+    void* inflater_user = nullptr;
+    int64_t by_callback = 0, by_host = 0;
     bool all_read() const { return coff >= std::min<uint64_t>(cend, file.size()); }
     const uint8_t* base() const { return pend ? pend->data() + pbeg : nullptr; }
     uint64_t avail() const { return pend_n - pbeg; }
@@ -863,7 +867,30 @@ int stream_fill(bcio_stream* s, uint64_t want) {
     auto next = std::make_unique<MapBuf>(keep + uoff + 64);
     if (!next->ok()) return fail(BCIO_E_IO, "cannot allocate the inflate buffer");
     if (keep) std::memcpy(next->data(), s->base(), keep);
-    if (!inflate_blocks(comp, blocks, next->data() + keep, s->nthreads)) return fail(BCIO_E_ZLIB, "inflate failed");
+    if (s->inflater && !blocks.empty()) {
+        // the inflater first; whatever it did not inflate (a non-zero status, or every block when
+        // the call itself fails) goes to the host inflater, whose verdict is the stream's
+        std::vector<bcio_zblock> zb(blocks.size());
+        for (size_t i = 0; i < blocks.size(); ++i)
+            zb[i] = bcio_zblock{blocks[i].coff, (uint32_t)blocks[i].clen, blocks[i].isize, blocks[i].uoff};
+        std::vector<uint8_t> status(blocks.size(), 1);
+        const int rc = s->inflater(s->inflater_user, comp, n, zb.data(), (int64_t)zb.size(), next->data() + keep, uoff,
+                                   status.data());
+        std::vector<Block> rest;
+        if (rc != 0) {
+            rest = blocks;
+        } else {
+            for (size_t i = 0; i < blocks.size(); ++i)
+                if (status[i] != 0) rest.push_back(blocks[i]);
+        }
+        s->by_callback += (int64_t)(blocks.size() - rest.size());
+        s->by_host += (int64_t)rest.size();
+        if (!rest.empty() && !inflate_blocks(comp, rest, next->data() + keep, s->nthreads))
+            return fail(BCIO_E_ZLIB, "inflate failed");
+    } else {
+        s->by_host += (int64_t)blocks.size();
+        if (!inflate_blocks(comp, blocks, next->data() + keep, s->nthreads)) return fail(BCIO_E_ZLIB, "inflate failed");
+    }
     s->pend = std::move(next);
     s->pend_n = keep + uoff - trim;
     s->pbeg = 0;
@@ -891,7 +918,9 @@ extern "C" int bcio_stream_open(const char* path, int nthreads, bcio_stream** ou
     if (orc == -1) return fail(BCIO_E_IO, std::string("cannot open ") + path);
     if (orc != 0) return fail(BCIO_E_IO, "short read");
     s->nthreads = hw_threads(nthreads);
-    uint64_t want = 256u << 10;
+    // one block first (a stream's inflater is set after the open: the blocks read here are the
+    // host's, and are only the header's), then doubling
+    uint64_t want = 1;
     for (;;) {  // the header, however many blocks it takes
         uint64_t q = 0;
         int rc = parse_header(s->base(), s->avail(), s->names, s->lens, &q);
@@ -902,9 +931,39 @@ extern "C" int bcio_stream_open(const char* path, int nthreads, bcio_stream** ou
         if (rc < 0) return rc;
         if (s->all_read()) return fail(BCIO_E_FORMAT, g_err);
         if ((rc = stream_fill(s.get(), want)) != BCIO_OK) return rc;
-        want *= 2;
+        want = std::max<uint64_t>(want * 2, 64u << 10);
     }
     *out = s.release();
+    return BCIO_OK;
+}
+
+static_assert(sizeof(bcio_zblock) == 24, "bcio_zblock is 24 bytes (bc_zblock has the same layout)");
+
+extern "C" int bcio_stream_set_inflater(bcio_stream* s, bcio_inflate_fn fn, void* user) {
+    if (!s) return fail(BCIO_E_ARG, "null argument");
+    s->inflater = fn;
+    s->inflater_user = fn ? user : nullptr;
+    return BCIO_OK;
+}
+
+extern "C" int bcio_stream_inflate_stats(const bcio_stream* s, int64_t* blocks_by_callback, int64_t* blocks_by_host) {
+    if (!s) return fail(BCIO_E_ARG, "null argument");
+    if (blocks_by_callback) *blocks_by_callback = s->by_callback;
+    if (blocks_by_host) *blocks_by_host = s->by_host;
+    return BCIO_OK;
+}
+
+extern "C" int bcio_inflate_blocks(const uint8_t* comp, uint64_t comp_bytes, const bcio_zblock* zb, int64_t n,
+                                   uint8_t* out, uint64_t out_bytes, int nthreads) {
+    if (n < 0 || (n > 0 && (!comp || !zb || !out))) return fail(BCIO_E_ARG, "null argument");
+    std::vector<Block> blocks((size_t)n);
+    for (int64_t i = 0; i < n; ++i) {
+        if (zb[i].isize > 65536 || zb[i].coff > comp_bytes || zb[i].clen > comp_bytes - zb[i].coff ||
+            zb[i].uoff > out_bytes || zb[i].isize > out_bytes - zb[i].uoff)
+            return fail(BCIO_E_ARG, "block outside its buffers");
+        blocks[(size_t)i] = Block{zb[i].coff, zb[i].clen, zb[i].uoff, zb[i].isize};
+    }
+    if (!inflate_blocks(comp, blocks, out, hw_threads(nthreads))) return fail(BCIO_E_ZLIB, "inflate failed");
     return BCIO_OK;
 }
 

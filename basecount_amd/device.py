@@ -48,6 +48,14 @@ class BcReads(C.Structure):
     ]
 
 
+class BcZBlock(C.Structure):
+    """bc_zblock (= bcio_zblock): one BGZF block's raw-DEFLATE bytes and where they inflate to."""
+    _fields_ = [("coff", C.c_uint64), ("clen", C.c_uint32), ("isize", C.c_uint32), ("uoff", C.c_uint64)]
+
+
+ZBLOCK_DTYPE = np.dtype([("coff", "<u8"), ("clen", "<u4"), ("isize", "<u4"), ("uoff", "<u8")])  # 24 bytes
+
+
 class BcPlan(C.Structure):
     _fields_ = [
         ("kernel", C.c_int32),  # BC_PLAN_RC 0 / BC_PLAN_SOLO 1 / BC_PLAN_TILES 2
@@ -131,6 +139,10 @@ def lib() -> C.CDLL:
         "bc_event_record": ([vp, C.c_int], C.c_int),
         "bc_ctx_wait": ([vp, vp], C.c_int),
         "bc_event_elapsed_ms": ([vp, C.c_int, C.c_int, C.POINTER(C.c_float)], C.c_int),
+        # BGZF inflate on the device (bc_inflate.hip)
+        "bc_bgzf_inflate": ([vp, vp, C.c_uint64, vp, i64, vp, C.c_uint64, vp], C.c_int),
+        "bc_bgzf_inflate_host": ([vp, vp, C.c_uint64, vp, i64, vp, C.c_uint64, vp], C.c_int),
+        "bc_bgzf_inflate_host_times": ([vp, C.POINTER(dbl * 3), C.POINTER(i64)], C.c_int),
         # multi-GPU (bc_comm.hip)
         "bc_comm_unique_id": ([vp], C.c_int),
         "bc_comm_init": ([vp, vp, C.c_int, C.c_int, C.POINTER(vp)], C.c_int),
@@ -403,6 +415,36 @@ class Context:
         check(lib().bc_pileup_segments(self.h, C.byref(r), int(n_seg), d_ref_len, d_read_beg, d_voff,
                                        int(virt_len), d_vpos, int(mbq), int(k), float(nf), float(nf2),
                                        d_counts, d_cov, d_pc, d_ent, d_sec, d_sum))
+
+    # BGZF inflate -------------------------------------------------------------------------
+    def bgzf_inflate(self, d_comp: int, comp_bytes: int, d_blocks: int, n: int, d_out: int, out_bytes: int,
+                     d_status: int) -> None:
+        """bc_bgzf_inflate: k_inflate over n device-resident bc_zblock descriptors (ZBLOCK_DTYPE),
+        stream-ordered; one status byte per block (0 = inflated)."""
+        check(lib().bc_bgzf_inflate(self.h, d_comp, int(comp_bytes), d_blocks, int(n), d_out, int(out_bytes),
+                                    d_status))
+
+    def bgzf_inflate_host(self, comp: np.ndarray, blocks: np.ndarray, out: np.ndarray) -> np.ndarray:
+        """bc_bgzf_inflate_host over host arrays (uint8 comp / out, ZBLOCK_DTYPE blocks): blocking;
+        returns the status bytes."""
+        assert comp.dtype == np.uint8 and out.dtype == np.uint8 and blocks.dtype == ZBLOCK_DTYPE
+        comp, blocks = np.ascontiguousarray(comp), np.ascontiguousarray(blocks)
+        assert out.flags.c_contiguous and out.flags.writeable
+        status = np.empty(max(1, blocks.size), np.uint8)
+        check(lib().bc_bgzf_inflate_host(self.h, comp.ctypes.data, comp.size, blocks.ctypes.data, blocks.size,
+                                         out.ctypes.data, out.size, status.ctypes.data))
+        return status[:blocks.size]
+
+    def bgzf_inflate_times(self) -> dict:
+        """Cumulative device time of this context's bgzf_inflate_host calls (ms) and their blocks."""
+        ms, nb = (C.c_double * 3)(), C.c_int64(0)
+        check(lib().bc_bgzf_inflate_host_times(self.h, C.byref(ms), C.byref(nb)))
+        return {"upload_ms": ms[0], "kernel_ms": ms[1], "download_ms": ms[2], "blocks": nb.value}
+
+    def inflater(self) -> tuple:
+        """(function address, context handle) for bcio_stream_set_inflater: the library's own
+        bc_bgzf_inflate_host, so no Python runs on the stream's fill path."""
+        return C.cast(lib().bc_bgzf_inflate_host, C.c_void_p).value, self.h
 
     def capture(self, fn) -> "Graph":
         """Record the compute calls made by fn() into a hipGraph (replay with Graph.launch)."""

@@ -70,6 +70,37 @@ def context(device: int | None = None) -> D.Context:
     return ctx
 
 
+# BASECOUNT_DEVICE_INFLATE=1: the streams' BGZF blocks are inflated by k_inflate (DESIGN.md §3,
+# "Device inflate") on a context of their own, so an inflate never waits behind counting kernels
+_INFLATE_CONTEXTS: dict = {}
+
+
+def device_inflate_on() -> bool:
+    return os.environ.get("BASECOUNT_DEVICE_INFLATE") not in (None, "", "0")
+
+
+def _open_stream(bam, device, **kw) -> BamStream:
+    if not device_inflate_on():
+        return BamStream(bam, **kw)
+    dev = default_device() if device is None else int(device)
+    ctx = _INFLATE_CONTEXTS.get(dev)
+    if ctx is None:
+        ctx = _INFLATE_CONTEXTS[dev] = D.Context(dev)
+    return BamStream(bam, device_inflate=ctx, **kw)
+
+
+def _note_inflate(stream) -> None:
+    """Add a stream's inflated-block counts to PLAN["inflate"] (before it is closed): the blocks of
+    its record fills; the few its open inflated on the host for the header are not counted, so
+    with the option on "host" is the number of blocks the device refused."""
+    st = stream.inflate_stats()
+    if not st["callback"] and not st["host"]:
+        return  # closed already
+    rec = PLAN.setdefault("inflate", {"device": 0, "host": 0})
+    rec["device"] += st["callback"] - stream.open_stats["callback"]
+    rec["host"] += st["host"] - stream.open_stats["host"]
+
+
 def norm_factors(k: int):
     """main.py:24-25: 1/log2(k), 1/log2(k-1) evaluated exactly as the reference does."""
     return 1 / math.log2(k), 1 / math.log2(k - 1)
@@ -268,6 +299,9 @@ def release_device_memory(only_unkept: bool = False) -> None:
             continue
         _SCRATCHES.pop(dev).release()
     for dev, ctx in _CONTEXTS.items():
+        if not (only_unkept and dev in _KEPT):
+            ctx.release_scratch()
+    for dev, ctx in _INFLATE_CONTEXTS.items():
         if not (only_unkept and dev in _KEPT):
             ctx.release_scratch()
     if not only_unkept:
@@ -700,6 +734,7 @@ def get_basecounts(bam, references=None, min_base_quality=0, min_mapping_quality
     Device memory: the call's HBM scratch (batch buffers, outputs; the results are on the host)
     is released when it returns, unless it runs inside the CLI (run(), one process per command)
     or ``_keep_scratch`` asks to keep it for the next call (release_device_memory() frees it)."""
+    PLAN["inflate"] = {"device": 0, "host": 0}  # BGZF blocks inflated by k_inflate / on the host
     try:
         return _get_basecounts_top(bam, references, min_base_quality, min_mapping_quality, chunk_size,
                                    show_n_bases, long_format, device, _mode, _tiles, _group)
@@ -736,7 +771,7 @@ def _get_basecounts_top(bam, references, min_base_quality, min_mapping_quality, 
 
 def _get_basecounts(bam, references, min_base_quality, min_mapping_quality, chunk_size, show_n_bases,
                     long_format, device, _mode, _tiles, _group, grouped, sharded=False):
-    stream = BamStream(bam)
+    stream = _open_stream(bam, device)
     try:
         references = get_references(stream, references)
         names = stream.references
@@ -783,18 +818,19 @@ def _get_basecounts(bam, references, min_base_quality, min_mapping_quality, chun
                 return find_ref_start(bam, c[0]) if c[1] == BOUND else find_ref_start(bam, c[0], c[1])
 
             with _phase("decode"):
+                _note_inflate(stream)
                 stream.close()
                 try:
                     beg = where(cuts[rk])
                     end = None if last else where(cuts[rk + 1])
                     if beg is None or (end is not None and end <= beg):
                         beg = end = None  # no records in this rank's range
-                    stream = BamStream(bam, voff_range=(beg, end))
+                    stream = _open_stream(bam, device, voff_range=(beg, end))
                 except (ValueError, OSError):
                     # a probe or the range open failed on this rank (a damaged block near a cut):
                     # a miss like any other, so every rank falls back to the whole-file decode,
                     # which raises the one process's error on every rank
-                    stream = BamStream(bam, voff_range=(None, None))
+                    stream = _open_stream(bam, device, voff_range=(None, None))
                     open_miss = True
         elif _group is not None:
             from .dist import shard
@@ -1059,6 +1095,7 @@ def _get_basecounts(bam, references, min_base_quality, min_mapping_quality, chun
             return out, owner, ref_order
         return out
     finally:
+        _note_inflate(stream)
         _release(stream)
 
 
@@ -1470,6 +1507,13 @@ def _timing_report(wall_s: float) -> None:
             print(f"basecount[{rank}] kernel {name}: {v[0]} launches, {v[1]:.2f} us mean", file=sys.stderr)
     for name, v in PHASES.items():
         print(f"basecount[{rank}] host {name}: {v * 1e3:.2f} ms", file=sys.stderr)
+    for ctx in _INFLATE_CONTEXTS.values():  # BASECOUNT_DEVICE_INFLATE=1: inside the decode phase
+        try:
+            t = ctx.bgzf_inflate_times()
+        except Exception:  # noqa: BLE001 - reporting must not mask the run's own outcome
+            continue
+        print(f"basecount[{rank}] device inflate: {t['blocks']} blocks, upload {t['upload_ms']:.2f} ms, "
+              f"kernel {t['kernel_ms']:.2f} ms, download {t['download_ms']:.2f} ms", file=sys.stderr)
     print(f"basecount[{rank}] wall {wall_s * 1e3:.2f} ms", file=sys.stderr)
 
 

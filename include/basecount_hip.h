@@ -438,6 +438,39 @@ int bc_pileup_summary_amplicons(bc_ctx* ctx, const bc_reads* d_reads, int64_t re
                                 double* d_sec, void* d_work, double* d_out, const int64_t* d_lo,
                                 const int64_t* d_hi, int32_t n_tiles, double* d_amp);
 
+/* ---- BGZF inflate on the device (opt-in; DESIGN.md §3 "Device inflate") ----------------------
+ * One descriptor per BGZF block: its raw-DEFLATE bytes are comp[coff, coff + clen) and inflate to
+ * exactly isize bytes (<= 65536) at out[uoff, uoff + isize).  Offsets have any byte alignment.  */
+typedef struct bc_zblock {
+    uint64_t coff;
+    uint32_t clen;
+    uint32_t isize;
+    uint64_t uoff;
+} bc_zblock; /* 24 bytes */
+
+/* k_inflate, one wave per block, stream-ordered (no host synchronisation).  All pointers are device
+ * memory; d_status gets one byte per block: 0 = inflated, else the reason (BC_Z_* of
+ * basecount_amd/csrc/bc_inflate.h: 1 descriptor outside its buffers or too large, 2..13 what
+ * zlib's inflate would refuse too).  Validity is zlib's: a block it refuses is refused here, and an
+ * accepted block holds the same bytes.  The kernel checks every descriptor itself against
+ * comp_bytes / out_bytes; a failing block is skipped, its own output bytes are unspecified and no
+ * byte outside out[uoff, uoff + isize) is written.  isize == 0 is fine and writes nothing.
+ * BC_E_ARG (before any device is touched): NULL pointer, n < 0 or n >= 2^31.                    */
+int bc_bgzf_inflate(bc_ctx* ctx, const uint8_t* d_comp, uint64_t comp_bytes, const bc_zblock* d_blocks, int64_t n,
+                    uint8_t* d_out, uint64_t out_bytes, uint8_t* d_status);
+/* The same from and to host memory, blocking: uploads the compressed span the blocks cover, runs
+ * k_inflate, downloads each block's bytes to h_out + uoff (bytes of h_out outside the blocks are
+ * not touched) and the statuses.  Works in slices of bounded inflated size; the device buffers are
+ * context scratch (grow-only, given back by bc_ctx_release_scratch).  Calls on one context are
+ * serialised.  `ctx` is a bc_ctx*: it is void* so that the symbol has the type of bcio.h's
+ * bcio_inflate_fn and can be handed to bcio_stream_set_inflater unchanged.                      */
+int bc_bgzf_inflate_host(void* ctx, const uint8_t* h_comp, uint64_t comp_bytes, const bc_zblock* h_blocks, int64_t n,
+                         uint8_t* h_out, uint64_t out_bytes, uint8_t* h_status);
+/* Device time of this context's bc_bgzf_inflate_host calls so far (hipEvent pairs on its stream),
+ * cumulative: ms[0] upload, ms[1] kernel, ms[2] download; *blocks the blocks handed in.  Either
+ * output may be NULL.                                                                           */
+int bc_bgzf_inflate_host_times(bc_ctx* ctx, double* ms /* [3] */, int64_t* blocks);
+
 /* ---- Multi-GPU: one process per GPU, RCCL over xGMI ---------------------------
  * Counting needs no exchange: references are independent, so each rank owns whole references
  * and runs the single-GPU path on them.  What crosses GPUs is small: the per-reference results

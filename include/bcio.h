@@ -120,6 +120,37 @@ const char* bcio_stream_ref_name(const bcio_stream* s, int32_t i);
 int64_t bcio_stream_ref_len(const bcio_stream* s, int32_t i);
 void bcio_stream_close(bcio_stream* s);
 
+/* ---- a stream's inflater ----------------------------------------------------------------------
+ * A stream inflates each fill's BGZF blocks on the host (nthreads threads).  An inflater, when
+ * set, is handed the fill's blocks first: comp[0, comp_bytes) is the mapped file, block i's
+ * raw-DEFLATE bytes are comp[coff, coff + clen) and inflate to exactly isize bytes at
+ * out[uoff, uoff + isize); it writes status[i] = 0 for every block it inflated and a non-zero
+ * byte for every block it did not (whose output bytes it may leave in any state).  The stream then
+ * inflates every block with a non-zero status on the host, and all of the fill's blocks when the
+ * call itself returns non-zero; only a host failure is BCIO_E_ZLIB "inflate failed", so the error
+ * behaviour of every file is the same with and without an inflater.  bcio_zblock has the layout of
+ * basecount_hip.h's bc_zblock, and bc_bgzf_inflate_host the type of bcio_inflate_fn: this library
+ * itself has no device dependency.  The blocks read by bcio_stream_open / _open_range before the
+ * inflater is set (the header's) are inflated on the host.
+ * bcio_stream_set_inflater: fn NULL = host only, as without the call.
+ * bcio_stream_inflate_stats: blocks inflated by the callback / on the host so far (the header's
+ * included in the latter); either output may be NULL.                                          */
+typedef struct bcio_zblock {
+    uint64_t coff;
+    uint32_t clen;
+    uint32_t isize;
+    uint64_t uoff;
+} bcio_zblock; /* 24 bytes */
+typedef int (*bcio_inflate_fn)(void* user, const uint8_t* comp, uint64_t comp_bytes, const bcio_zblock* blocks,
+                               int64_t n, uint8_t* out, uint64_t out_bytes, uint8_t* status);
+int bcio_stream_set_inflater(bcio_stream* s, bcio_inflate_fn fn, void* user);
+int bcio_stream_inflate_stats(const bcio_stream* s, int64_t* blocks_by_callback, int64_t* blocks_by_host);
+/* The streams' own host inflater on caller-made descriptors, nthreads threads (<= 0: hardware):
+ * for measurements and tests.  BCIO_E_ARG for a descriptor outside its buffers, BCIO_E_ZLIB
+ * "inflate failed" when any block does not inflate to exactly isize bytes.                      */
+int bcio_inflate_blocks(const uint8_t* comp, uint64_t comp_bytes, const bcio_zblock* blocks, int64_t n, uint8_t* out,
+                        uint64_t out_bytes, int nthreads);
+
 /* ---- one file decoded by several ranks (each only its own references' records) ----------------
  * Positions are BAM virtual offsets: (BGZF block file offset << 16) | offset in its inflated bytes.
  * bcio_find_ref_start: the position of the first record whose refID is >= tid or -1 (unmapped),
