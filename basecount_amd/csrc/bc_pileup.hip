@@ -8,7 +8,8 @@
 //     lane = (window g = lane >> 3, read slot s = lane & 7):
 // the lane assembles the 8 event classes its read has in reference window [t0+8g, t0+8g+8) as
 // ONE 32-bit word (a funnel shift of the BC_SEQ_EVENT sequence per CIGAR run, deletions as class
-// 1100) and counts all 8 positions x 6 columns with SWAR nibble counters: ~30 VALU per 8 bases.
+// 1100) and counts all 8 positions x 6 columns with bit-plane counters (bc_planes.h; without a
+// quality threshold at 32-bit indices) or SWAR nibble counters: ~22 / ~30 VALU per 8 bases.
 // No atomics and no histogram memset: the 8 read slots are reduced with DPP, the S waves of a
 // group through LDS atomics, and the per-position statistics of main.py:29-53 are computed in the
 // same launch (kernel 2 fused: tile_tail, every wave of the group finishing and storing its own
@@ -154,6 +155,7 @@ __global__ __launch_bounds__(512, 4) void k_pileup(TileArgs A) {
     const IT L = (IT)A.L;
     const int s8 = lane & 7;
     const bool qual_vec = ((uintptr_t)A.qual & 15u) == 0;
+    constexpr bool PLANES = !QUAL && sizeof(IT) == 4;  // bit-plane counters (bc_walk.h: WalkCounters)
     if (STATS && S == 1) {  // no barrier per tile: the table is copied once
         if (threadIdx.x < 128) tab[threadIdx.x] = ((const double2*)log2d::kTab)[threadIdx.x];
         __syncthreads();
@@ -228,10 +230,8 @@ __global__ __launch_bounds__(512, 4) void k_pileup(TileArgs A) {
             }
             unsigned long long acc = 0;
             int pending = 0;
-            Swar W;
-#pragma unroll
-            for (int c = 0; c < 6; ++c) W.a4[c] = 0;
-            int it4 = 0;
+            typename WalkCounters<PLANES>::type W;
+            counters_zero(W);
             uint4* myrec = rec_all + wave * kTile * 3;
             uint8_t* mystage = stage_all + (size_t)wave * kStageRegion + 16;
             auto chunk_nr = [&](IT b) { return b < hi ? (int)((hi - b) < 64 ? (hi - b) : 64) : 0; };
@@ -242,8 +242,8 @@ __global__ __launch_bounds__(512, 4) void k_pileup(TileArgs A) {
 #endif
             for (; base < hi; base += (IT)S * 64) {
                 const IT nb = base + (IT)S * 64;
-                process_chunk<QUAL, K>(A, base, chunk_nr(base), F, nb, chunk_nr(nb), lane, s8, gb, t0, P, edge,
-                                       beyond, bmask, myrec, mystage, qual_vec, W, it4, cnt, acc, pending, bad);
+                process_chunk<QUAL, K, PLANES>(A, base, chunk_nr(base), F, nb, chunk_nr(nb), lane, s8, gb, t0, P, edge,
+                                       beyond, bmask, myrec, mystage, qual_vec, W, cnt, acc, pending, bad);
                 __builtin_amdgcn_wave_barrier();
 #ifdef BC_PHASE_TRACE
                 if (nch < 2) trace_stamp(A, 2 + nch);
@@ -251,7 +251,7 @@ __global__ __launch_bounds__(512, 4) void k_pileup(TileArgs A) {
 #endif
             }
             flush_acc(acc, cnt);
-            if (it4) swar_fold<K>(W, cnt, s8);
+            counters_finish<K>(W, cnt, s8);
             if (edge) {  // first offending read of this tile (std::out_of_range in the reference)
                 for (int o = 32; o > 0; o >>= 1) {
                     const int64_t b2 = __shfl_down(bad, o);
@@ -488,19 +488,17 @@ __global__ __launch_bounds__(256, 4) void k_pileup_solo(PileArgs A) {
             }
             unsigned long long acc = 0;
             int pending = 0;
-            Swar W;
-#pragma unroll
-            for (int c = 0; c < 6; ++c) W.a4[c] = 0;
-            int it4 = 0;
+            SwarCnt W;
+            counters_zero(W);
             auto chunk_nr = [&](int64_t b) { return b < hi ? (int)((hi - b) < 64 ? (hi - b) : 64) : 0; };
             ReadFields F = load_fields(A, lo, chunk_nr(lo), lane);
             for (int64_t base = lo; base < (int64_t)hi; base += 64) {
-                process_chunk<QUAL, K>(A, base, chunk_nr(base), F, base + 64, chunk_nr(base + 64), lane, s8, gb, t0, P,
-                                       edge, beyond, bmask, myrec, mystage, qual_vec, W, it4, cnt, acc, pending, bad);
+                process_chunk<QUAL, K, false>(A, base, chunk_nr(base), F, base + 64, chunk_nr(base + 64), lane, s8, gb, t0, P,
+                                       edge, beyond, bmask, myrec, mystage, qual_vec, W, cnt, acc, pending, bad);
                 __builtin_amdgcn_wave_barrier();
             }
             flush_acc(acc, cnt);
-            if (it4) swar_fold<K>(W, cnt, s8);
+            counters_finish<K>(W, cnt, s8);
             if (edge) {
                 for (int o = 32; o > 0; o >>= 1) {
                     const int64_t b2 = __shfl_down(bad, o);

@@ -141,19 +141,17 @@ __device__ __forceinline__ void tile_counts(const PileArgs& A, int64_t t, int la
     }
     unsigned long long acc = 0;
     int pending = 0;
-    Swar W;
-#pragma unroll
-    for (int c = 0; c < 6; ++c) W.a4[c] = 0;
-    int it4 = 0;
+    SwarCnt W;
+    counters_zero(W);
     auto chunk_nr = [&](int64_t b) { return b < hi ? (int)((hi - b) < 64 ? (hi - b) : 64) : 0; };
     ReadFields F = load_fields(A, lo, chunk_nr(lo), lane);
     for (int64_t base = lo; base < hi; base += 64) {
-        process_chunk<QUAL, K>(A, base, chunk_nr(base), F, base + 64, chunk_nr(base + 64), lane, s8, gb, t0, P, edge,
-                               beyond, bmask, myrec, mystage, qual_vec, W, it4, cnt, acc, pending, bad);
+        process_chunk<QUAL, K, false>(A, base, chunk_nr(base), F, base + 64, chunk_nr(base + 64), lane, s8, gb, t0, P, edge,
+                               beyond, bmask, myrec, mystage, qual_vec, W, cnt, acc, pending, bad);
         __builtin_amdgcn_wave_barrier();
     }
     flush_acc(acc, cnt);
-    if (it4) swar_fold<K>(W, cnt, s8);
+    counters_finish<K>(W, cnt, s8);
     if (edge) {
         for (int o = 32; o > 0; o >>= 1) {
             const int64_t b2 = __shfl_down(bad, o);

@@ -1,6 +1,6 @@
 // bc_tile.h — the position-tiled walk shared by the fused pileup kernels (bc_pileup.hip) and the
 // read-parallel summary (bc_sum.hip): kernel arguments, the per-chunk CIGAR decode + staging +
-// SWAR walk of one 64-position tile (process_chunk), the read-range search and numpy's leaf
+// bit-plane walk of one 64-position tile (process_chunk), the read-range search and numpy's leaf
 // sums.  Included once per translation unit (anonymous namespace: each gets its own copy).
 #pragma once
 #include <cstdio>
@@ -275,13 +275,14 @@ __device__ __forceinline__ void walk_complex(const TileArgs& A, const uint4* rec
     }
 }
 
-// Walk a chunk of nr reads (records padded with empty ones to 64) with lane = (window g, read
+// The walk of the instances that keep the SWAR counters (read-relative records, window_events;
+// see WalkCounters in bc_walk.h).  Walk a chunk of nr reads (records padded with empty ones to 64) with lane = (window g, read
 // slot s): reads it*8 + s and it*8 + 8 + s in step it (two independent LDS chains in flight;
 // rounding the steps up to even only ever touches padding records).  NR: the chunk's largest
 // run count (1, 2, 4).  nr and it4 are wave-uniform.
 template <int NR, bool GAP, bool STAGED, bool QUAL, int NC>
 __device__ __forceinline__ void walk_swar(const TileArgs& A, const uint4* rec, const uint32_t* words, int nr, int gb,
-                                          int s8, int64_t rbase, bool edge, uint32_t bmask, Swar& W, int& it4,
+                                          int s8, int64_t rbase, bool edge, uint32_t bmask, SwarCnt& C,
                                           uint32_t (&cnt)[6], int64_t& bad) {
     const SeqSrc src{words, STAGED ? (int64_t)(kStage / 4) : A.seq_words, A.qual, A.qual_bytes, A.mbq};
     const int iters = (((nr + 7) >> 3) + 1) & ~1;
@@ -295,14 +296,50 @@ __device__ __forceinline__ void walk_swar(const TileArgs& A, const uint4* rec, c
             x0 &= ~bmask;
             x1 &= ~bmask;
         }
-        swar_add<NC>(W, x0);
-        swar_add<NC>(W, x1);
-        it4 += 2;
-        if (it4 >= 14) {  // every a4 field <= 14
-            swar_fold<NC>(W, cnt, s8);
-            it4 = 0;
-        }
+        counters_add<GAP, NC>(C, x0, x1, cnt, s8);
     }
+}
+
+// Walk a chunk of nr reads (records padded with empty ones to 64) with lane = (window g, read
+// slot s): reads it*8 + s and it*8 + 8 + s in step it (two independent LDS chains in flight;
+// rounding the steps up to even only ever touches padding records).  NR: the chunk's largest
+// run count (1, 2, 4).  nr and the counters' fold counts are wave-uniform.  c32 = 32 * g: the lane's
+// window as a nibble-bit offset from the tile's first position.
+template <int NR, bool GAP, bool STAGED, int NC>
+__device__ __forceinline__ void walk_planes(const TileArgs& A, const uint4* rec, const uint32_t* words, int nr, int c32,
+                                            int s8, int64_t rbase, bool edge, uint32_t bmask, Planes& W,
+                                            uint32_t (&cnt)[6], int64_t& bad) {
+    const SeqSrc src{words, STAGED ? (int64_t)(kStage / 4) : A.seq_words, A.qual, A.qual_bytes, A.mbq};
+    const int iters = (((nr + 7) >> 3) + 1) & ~1;
+#pragma unroll 1
+    for (int it = 0; it < iters; it += 2) {
+        const int r0 = it * 8 + s8, r1 = r0 + 8;
+        uint32_t x0 = tile_events<NR, GAP, STAGED>(src, rec, r0, c32);
+        uint32_t x1 = tile_events<NR, GAP, STAGED>(src, rec, r1, c32);
+        if (edge) {  // events at positions >= L: the reference's out_of_range
+            if ((x0 & bmask) && rbase + r0 < bad) bad = rbase + r0;
+            if ((x1 & bmask) && rbase + r1 < bad) bad = rbase + r1;
+            x0 &= ~bmask;
+            x1 &= ~bmask;
+        }
+        counters_add<GAP, NC>(W, x0, x1, cnt, s8);
+    }
+}
+
+// the walk of the counters' kind (overloads)
+template <int NR, bool GAP, bool STAGED, bool QUAL, int NC>
+__device__ __forceinline__ void walk_counters(const TileArgs& A, const uint4* rec, const uint32_t* words, int nr,
+                                              int /* gb: the SWAR walk's */, int s8, int64_t rbase, bool edge,
+                                              uint32_t bmask, Planes& W, uint32_t (&cnt)[6], int64_t& bad) {
+    static_assert(!QUAL, "the planes walk applies no quality mask");
+    const int c32 = (int)(threadIdx.x & 56u) * 4;  // 32 * (lane >> 3)
+    walk_planes<NR, GAP, STAGED, NC>(A, rec, words, nr, c32, s8, rbase, edge, bmask, W, cnt, bad);
+}
+template <int NR, bool GAP, bool STAGED, bool QUAL, int NC>
+__device__ __forceinline__ void walk_counters(const TileArgs& A, const uint4* rec, const uint32_t* words, int nr, int gb,
+                                              int s8, int64_t rbase, bool edge, uint32_t bmask, SwarCnt& C,
+                                              uint32_t (&cnt)[6], int64_t& bad) {
+    walk_swar<NR, GAP, STAGED, QUAL, NC>(A, rec, words, nr, gb, s8, rbase, edge, bmask, C, cnt, bad);
 }
 
 constexpr int kFinBytes = 6 * kTile * 4;  // a group's reduced counts
@@ -376,8 +413,8 @@ constexpr uint32_t kSpecSlack = 128;  // bytes staged beyond the last read's fir
 
 // One chunk of nr <= 64 reads [base, base + nr) of a tile, walked by one wave: decode the reads'
 // CIGARs (fields F were loaded one chunk ahead), stage their sequence into the wave's LDS region
-// and walk them (SWAR windows, or the per-position CIGAR walk for complex reads).  Counts
-// accumulate in W / cnt (lane = tile position t0 + lane), the first out-of-range read in `bad`.
+// and walk them (bit-plane window counters, or the per-position CIGAR walk for complex reads).
+// Counts accumulate in W / cnt (lane = tile position t0 + lane), the first out-of-range read in `bad`.
 // On return F holds the fields of the wave's next chunk [next_base, next_base + next_nr),
 // loaded while this chunk is walked.
 //
@@ -385,11 +422,12 @@ constexpr uint32_t kSpecSlack = 128;  // bytes staged beyond the last read's fir
 // batch usually lie in file order: [first read's seq, last read's seq + slack)) by LDS-DMA,
 // issued together with the CIGAR loads, so a chunk costs one memory round trip before its walk;
 // the exact segment, known after the decode, is restaged only when it is not covered.
-template <bool QUAL, int K>
+template <bool QUAL, int K, bool PLANES>
 __device__ __forceinline__ void process_chunk(const TileArgs& A, int64_t base, int nr, ReadFields& F,
                                               int64_t next_base, int next_nr, int lane, int s8, int gb, int64_t t0,
                                               int64_t P, bool edge, bool beyond, uint32_t bmask, uint4* myrec,
-                                              uint8_t* mystage, bool qual_vec, Swar& W, int& it4, uint32_t (&cnt)[6],
+                                              uint8_t* mystage, bool qual_vec, typename WalkCounters<PLANES>::type& W,
+                                              uint32_t (&cnt)[6],
                                               unsigned long long& acc, int& pending, int64_t& bad) {
     // ---- chunk load: CIGAR -> run table (VALU), speculative staging in flight meanwhile
     RunTable T;
@@ -444,7 +482,7 @@ __device__ __forceinline__ void process_chunk(const TileArgs& A, int64_t base, i
     const uint32_t qbase = staged ? 2u * seg_lo : 0u;
     if (cx) {  // walk_complex reads {pos, absolute seq_nib}
         myrec[lane * 3] = make_uint4(mpos, msn, 0u, 0u);
-    } else {
+    } else if (!PLANES) {  // read-relative records (window_events)
         uint32_t rr[kMaxRuns], nb[kMaxRuns];
 #pragma unroll
         for (int k = 0; k < kMaxRuns; ++k) {
@@ -454,6 +492,30 @@ __device__ __forceinline__ void process_chunk(const TileArgs& A, int64_t base, i
         myrec[lane * 3] = make_uint4(mpos, T.span * 4u, rr[0], nb[0]);
         myrec[lane * 3 + 1] = make_uint4(rr[1], nb[1], rr[2], nb[2]);
         myrec[lane * 3 + 2] = make_uint4(rr[3], nb[3], 0u, 0u);
+    } else {
+        // tile-relative records (bc_walk.h): what a window needs of a read, with everything that
+        // is constant per (read, tile) computed here, once.  (Modular 32-bit arithmetic: the
+        // differences are small whenever the read is a real one; a padding lane's runs are empty.)
+        const uint32_t rel = mpos - (uint32_t)t0;  // pos - t0
+        const uint32_t rel4 = rel * 4u;
+        const uint32_t gp = pack_tile_rr((int)rel4, (int)(rel4 + T.span * 4u));
+        uint32_t nb[kMaxRuns];
+#pragma unroll
+        for (int k = 0; k < kMaxRuns; ++k) {
+            nb[k] = msn - qbase + (uint32_t)T.qd[k] - rel;  // the base at the tile's first position
+            if (staged) nb[k] *= 4u;
+        }
+        if (maxrun <= 1) {
+            myrec[lane * 3] = make_uint4(rel4 + T.st[0] * 4u, rel4 + T.en[0] * 4u, nb[0], gp);
+        } else {
+            uint32_t rr[kMaxRuns];
+#pragma unroll
+            for (int k = 0; k < kMaxRuns; ++k)
+                rr[k] = pack_tile_rr((int)(rel4 + T.st[k] * 4u), (int)(rel4 + T.en[k] * 4u));
+            myrec[lane * 3] = make_uint4(gp, 0u, rr[0], nb[0]);
+            myrec[lane * 3 + 1] = make_uint4(rr[1], nb[1], rr[2], nb[2]);
+            myrec[lane * 3 + 2] = make_uint4(rr[3], nb[3], 0u, 0u);
+        }
     }
     if (dma) stage_wait();  // LDS-DMA landed (hipcc does not track it)
     F = load_fields(A, next_base, next_nr, lane);  // in flight during the walk
@@ -470,8 +532,8 @@ __device__ __forceinline__ void process_chunk(const TileArgs& A, int64_t base, i
     } else {
         // separate calls keep the LDS / global address spaces visible to the compiler
 #define BC_WALK(NR, GP, ST)                                                                                 \
-walk_swar<NR, GP, ST, QUAL, K>(A, myrec, ST ? (const uint32_t*)mystage : (const uint32_t*)A.seq, nr, gb,   \
-                       s8, rbase, edge, bmask, W, it4, cnt, bad)
+walk_counters<NR, GP, ST, QUAL, K>(A, myrec, ST ? (const uint32_t*)mystage : (const uint32_t*)A.seq, nr, gb,     \
+                     s8, rbase, edge, bmask, W, cnt, bad)
 #define BC_WALK_NR(GP, ST)                                                                                  \
 do {                                                                                                    \
 if (maxrun <= 1) BC_WALK(1, GP, ST);                                                                \
@@ -487,6 +549,7 @@ else BC_WALK(4, GP, ST);                                                        
         }
 #undef BC_WALK_NR
 #undef BC_WALK
+        counters_reserve<K>(W, cnt, s8);  // room for the next chunk
     }
 }
 

@@ -1,6 +1,7 @@
 // bc_walk.h — device building blocks shared by the two pileup kernels (the position-tiled
 // k_pileup and the read-chunked k_rc): CIGAR run tables, the BC_SEQ_EVENT window fetch and the
-// SWAR window counters.  Included inside namespace bc::{anonymous} of each kernel file.
+// SWAR window counters (k_rc's run-table walk) and the bit-plane window counters of the tiled walk
+// (bc_planes.h).  Included inside namespace bc::{anonymous} of each kernel file.
 //
 // Event classes (BC_SEQ_EVENT, include/basecount_hip.h): one nibble per base,
 //   A 0001, C 0010, G 0100, T 1000, N 0011, not counted 0000, and, synthesized by the walk for
@@ -10,9 +11,9 @@
 #pragma once
 
 #include "bc_runs.h"
+#include "bc_planes.h"
 
 constexpr unsigned long long kNibCol6 = 0x6666666366625106ull;  // class -> column, 6 = none
-constexpr uint32_t kM1 = 0x11111111u;      // bit 0 of every nibble
 constexpr uint32_t kClsDel = 0xCCCCCCCCu;  // class 1100 (deletion / ref-skip) in every nibble
 constexpr uint32_t kNone = 0xFFFFFFFFu;  // packed event: none
 constexpr uint32_t kDel = 0x80000000u;   // packed event: deletion / ref-skip
@@ -81,6 +82,158 @@ __device__ __forceinline__ void swar_fold(Swar& W, uint32_t (&cnt)[6], int s8) {
         cnt[c] += (((s8 & 1) ? b1 : b0) >> (8 * (s8 >> 1))) & 0xFFu;
         W.a4[c] = 0;
     }
+}
+
+// ---- bit-plane counters of a lane's 8-position window (the tiled walk; bc_planes.h) --------
+// p[]: the vertical counters of the 32 bits of the window words; fn / fd: nibble counters of the N
+// and deletion flags (the two classes that are not one-hot).  na / nf: reads added since the
+// planes' / the fix-up's last fold (wave-uniform).
+struct Planes {
+    uint32_t p[kPlanes];
+    uint32_t fn, fd;
+    int na, nf;
+};
+__device__ __forceinline__ void planes_zero(Planes& W) {
+#pragma unroll
+    for (int j = 0; j < kPlanes; ++j) W.p[j] = 0;
+    W.fn = W.fd = 0;
+    W.na = W.nf = 0;
+}
+
+// Two reads' window words into the counters (GAP: the walk can produce deletions).
+template <bool GAP>
+__device__ __forceinline__ void planes_add(Planes& W, uint32_t x0, uint32_t x1) {
+    planes_add2(W.p, x0, x1);
+    W.fn += fix_n(x0) + fix_n(x1);
+    if (GAP) W.fd += fix_d(x0) + fix_d(x1);
+    W.na += 2;
+    W.nf += 2;
+}
+
+template <int CTRL>
+__device__ __forceinline__ uint32_t dpp_of(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, false);
+}
+// one bit of a + (a of the lane CTRL names) with carry c (planes_join's adder, one plane at a time)
+template <int CTRL>
+__device__ __forceinline__ uint32_t join_bit(uint32_t a, uint32_t& c) {
+    const uint32_t b = dpp_of<CTRL>(a), s = bit_xor3(a, b, c);
+    c = bit_maj(a, b, c);
+    return s;
+}
+
+// one fix-up nibble counter summed over the 8 read slots, at this lane's own position
+__device__ __forceinline__ uint32_t fix_sum(uint32_t f, int s8) {
+    const uint32_t b0 = sum8(f & 0x0F0F0F0Fu), b1 = sum8((f >> 4) & 0x0F0F0F0Fu);
+    return (((s8 & 1) ? b1 : b0) >> (8 * (s8 >> 1))) & 0xFFu;
+}
+
+// Fold the fix-up counters into cnt[] of this lane's own position (8g + s == lane): the N and
+// deletion columns gain them, the planes they were counted in lose them (cnt[] is exact modulo
+// 2^32 once the planes are folded too: planes_fold).  A counter no lane has touched (every chunk
+// of an all-ACGT, all-M batch) is skipped.  Must be called by the whole wave.
+template <int NC>
+__device__ __forceinline__ void fix_fold(Planes& W, uint32_t (&cnt)[6], int s8) {
+    if (__any(W.fn != 0u)) {
+        const uint32_t n = fix_sum(W.fn, s8);
+        cnt[0] -= n;
+        cnt[1] -= n;
+        if (NC == 6) cnt[5] += n;
+        W.fn = 0;
+    }
+    if (__any(W.fd != 0u)) {
+        const uint32_t d = fix_sum(W.fd, s8);
+        cnt[2] -= d;
+        cnt[3] -= d;
+        cnt[4] += d;
+        W.fd = 0;
+    }
+    W.nf = 0;
+}
+
+// Fold the planes (and the fix-up) into cnt[]: the 8 read slots' planes are added bit-sliced
+// (quad xor 1, quad xor 2, half-row mirror: every lane of the window ends with the 8-plane sums),
+// and the lane takes its own position's four sums.  Must be called by the whole wave.
+template <int NC>
+__device__ __forceinline__ void planes_fold(Planes& W, uint32_t (&cnt)[6], int s8) {
+    // planes_join three times and planes_counts (bc_planes.h), plane by plane through all three
+    // steps: a plane of a partial sum is dead as soon as the next step has taken it (the steps one
+    // after the other keep 15 planes alive at once, which the kernels' registers do not have)
+    uint32_t c1 = 0, c2 = 0, c3 = 0, by = 0;
+#pragma unroll
+    for (int j = 0; j < kSumPlanes; ++j) {
+        const uint32_t s6 = j < kPlanes ? join_bit<0xB1>(W.p[j], c1) : c1;       // j <= kPlanes
+        const uint32_t s7 = j <= kPlanes ? join_bit<0x4E>(s6, c2) : c2;          // j <= kPlanes + 1
+        const uint32_t s8p = j <= kPlanes + 1 ? join_bit<0x141>(s7, c3) : c3;    // j <= kPlanes + 2
+        by += plane_spread(s8p, s8) << j;
+    }
+    cnt[0] += by & 0xFFu;
+    cnt[1] += (by >> 8) & 0xFFu;
+    cnt[2] += (by >> 16) & 0xFFu;
+    cnt[3] += by >> 24;
+#pragma unroll
+    for (int j = 0; j < kPlanes; ++j) W.p[j] = 0;
+    W.na = 0;
+    fix_fold<NC>(W, cnt, s8);
+}
+
+// ---- the tiled walk's counters: planes, or the SWAR nibble counters -------------------------
+// PLANES is k_pileup without a quality threshold at 32-bit indices (the C2 kernel and its k / STATS
+// siblings).  Every other instance of the tiled walk (a quality threshold, 64-bit indices, the
+// sparse sweep k_pileup_solo, bc_sum.hip) sits at or next to the 128-VGPR limit, where the planes
+// walk costs spilled registers: those keep the read-relative records and the
+// SWAR counters, at most 14 reads added (it4) before swar_fold, every a4 nibble <= 14.
+struct SwarCnt {
+    Swar W;
+    int it4;
+};
+template <bool PLANES>
+struct WalkCounters {
+    typedef SwarCnt type;
+};
+template <>
+struct WalkCounters<true> {
+    typedef Planes type;
+};
+__device__ __forceinline__ void counters_zero(Planes& W) { planes_zero(W); }
+__device__ __forceinline__ void counters_zero(SwarCnt& C) {
+#pragma unroll
+    for (int c = 0; c < 6; ++c) C.W.a4[c] = 0;
+    C.it4 = 0;
+}
+// After a chunk's walk: make room for the kChunkAdds reads the next chunk can add to a lane.  The planes'
+// folds are here and not in the walk's loop (a conditional fold there makes the loop carry copies
+// of cnt[]); the SWAR counters fold in the loop, after 14 reads.
+template <int NC>
+__device__ __forceinline__ void counters_reserve(Planes& W, uint32_t (&cnt)[6], int s8) {
+    if (W.na + kChunkAdds > kPlaneAdds) planes_fold<NC>(W, cnt, s8);
+    else if (W.nf + kChunkAdds > kFixAdds) fix_fold<NC>(W, cnt, s8);
+}
+template <int NC>
+__device__ __forceinline__ void counters_reserve(SwarCnt&, uint32_t (&)[6], int) {}
+// two reads' window words of one walk step (SWAR: and the fold that is due after them)
+template <bool GAP, int NC>
+__device__ __forceinline__ void counters_add(Planes& W, uint32_t x0, uint32_t x1, uint32_t (&cnt)[6], int s8) {
+    planes_add<GAP>(W, x0, x1);
+}
+template <bool GAP, int NC>
+__device__ __forceinline__ void counters_add(SwarCnt& C, uint32_t x0, uint32_t x1, uint32_t (&cnt)[6], int s8) {
+    swar_add<NC>(C.W, x0);
+    swar_add<NC>(C.W, x1);
+    C.it4 += 2;
+    if (C.it4 >= 14) {  // every a4 field <= 14
+        swar_fold<NC>(C.W, cnt, s8);
+        C.it4 = 0;
+    }
+}
+// at the end of a tile (planes: nf <= na, and their fold takes the fix-up with it)
+template <int NC>
+__device__ __forceinline__ void counters_finish(Planes& W, uint32_t (&cnt)[6], int s8) {
+    if (W.na) planes_fold<NC>(W, cnt, s8);
+}
+template <int NC>
+__device__ __forceinline__ void counters_finish(SwarCnt& C, uint32_t (&cnt)[6], int s8) {
+    if (C.it4) swar_fold<NC>(C.W, cnt, s8);
 }
 
 // SWAR mask of 8 bases that pass the quality test, from their 8 quality bytes (q0: bases 0-3).
@@ -207,3 +360,68 @@ __device__ __forceinline__ uint32_t window_events(const SeqSrc& S, const uint4* 
     return x;
 }
 
+// ---- tile-relative walk records (the tiled walk: process_chunk writes them, bc_tile.h) ------
+// Everything that is constant per (read, tile) is computed once, by the lane that builds the
+// record: the run bounds as nibble-bit offsets from the tile's first position,
+//   lo4 = 4 * (pos + st - t0),  hi4 = 4 * (pos + en - t0),
+// and `nb`, the index of the base the read has at the tile's first position (the run's base at
+// reference offset t0 - pos): staged, 4 x the nibble index relative to the stage (a bit index: its
+// low 5 bits are the funnel shift of every window of the read); unstaged, the nibble index in the
+// whole BC_SEQ_EVENT buffer (int32, widened by the fetch).  A window (lane constant c32 =
+// 32 * (lane >> 3)) subtracts c32, clamps to [0, 32] and builds the mask.
+//   single-run chunks (NR = 1), one uint4:  {lo4, hi4, nb, gp}     (plain int32, not clamped)
+//   NR = 2, 4, three uint4:  [0] = {gp, 0, rr0, nb0}  [1] = {rr1, nb1, rr2, nb2}  [2] = {rr3, nb3, 0, 0}
+// rr = lo4 | hi4 << 16 and gp (the read's own range [pos, pos + span), for the deletions of GAP
+// walks) = lo4 | hi4 << 16, both ends clamped to the tile [0, 256] by the record's lane.
+__device__ __forceinline__ uint32_t tile_clamp(int v4) { return (uint32_t)(v4 < 0 ? 0 : (v4 > 256 ? 256 : v4)); }
+__device__ __forceinline__ uint32_t pack_tile_rr(int lo4, int hi4) { return tile_clamp(lo4) | (tile_clamp(hi4) << 16); }
+
+// mask of the window nibbles in [lo4, hi4) (tile-relative, lo4 <= hi4)
+__device__ __forceinline__ uint32_t tile_mask(int lo4, int hi4, int c32) {
+    int kl = (int)((uint32_t)lo4 - (uint32_t)c32), kh = (int)((uint32_t)hi4 - (uint32_t)c32);  // (modular)
+    kl = kl < 0 ? 0 : (kl > 32 ? 32 : kl);
+    kh = kh < 0 ? 0 : (kh > 32 ? 32 : kh);
+    return lo32_bit(kh) - lo32_bit(kl);
+}
+
+// The 8 event classes from index nb (see above) + the window's offset.  (No quality mask: the
+// planes walk is instantiated without a quality threshold only.)
+template <bool STAGED>
+__device__ __forceinline__ uint32_t tile_fetch(const SeqSrc& S, uint32_t nb, int c32) {
+    if (STAGED) {
+        // windows that matter start at bit >= -28; anything else is masked off after the fetch
+        const int b = (int)nb + c32, lim = (int)S.lim;
+        int w0 = b >> 5;
+        w0 = w0 < -1 ? -1 : (w0 > lim ? lim : w0);
+        return __builtin_amdgcn_alignbit(S.words[w0 + 1], S.words[w0], (uint32_t)b);
+    }
+    const int64_t n0 = (int64_t)(int32_t)nb + (c32 >> 2);
+    return fetch8<false>(S, n0);
+}
+
+// The 8 event classes (x) read r has in the lane's window: its M runs' bases (one funnel-shifted
+// fetch each) and, GAP, class 1100 on the rest of its range.
+template <int NR, bool GAP, bool STAGED>
+__device__ __forceinline__ uint32_t tile_events(const SeqSrc& S, const uint4* rec, int r, int c32) {
+    const uint4 a = rec[r * 3];
+    if (NR == 1) {
+        const uint32_t m = tile_mask((int)a.x, (int)a.y, c32);
+        uint32_t x = tile_fetch<STAGED>(S, a.z, c32) & m;
+        if (GAP) x |= kClsDel & tile_mask((int)(a.w & 0xFFFFu), (int)(a.w >> 16), c32) & ~m;
+        return x;
+    }
+    const uint4 b = rec[r * 3 + 1];
+    uint2 c = make_uint2(0u, 0u);
+    if (NR > 2) c = *(const uint2*)&rec[r * 3 + 2];
+    const uint32_t rr[4] = {a.z, b.x, b.z, c.x};
+    const uint32_t nb[4] = {a.w, b.y, b.w, c.y};
+    uint32_t x = 0, mm = 0;
+#pragma unroll
+    for (int k = 0; k < NR; ++k) {
+        const uint32_t m = tile_mask((int)(rr[k] & 0xFFFFu), (int)(rr[k] >> 16), c32);
+        x |= tile_fetch<STAGED>(S, nb[k], c32) & m;
+        if (GAP) mm |= m;
+    }
+    if (GAP) x |= kClsDel & tile_mask((int)(a.x & 0xFFFFu), (int)(a.x >> 16), c32) & ~mm;
+    return x;
+}
