@@ -76,6 +76,12 @@ class BcioSelection(C.Structure):
     ]
 
 
+class BcioDecoder(C.Structure):
+    """bcio_decoder: a stream's record decoder as four callbacks (function addresses) and their user."""
+    _fields_ = [("user", C.c_void_p), ("fill", C.c_void_p), ("next", C.c_void_p), ("pending", C.c_void_p),
+                ("release", C.c_void_p)]
+
+
 class BcioWriteSpec(C.Structure):
     _fields_ = [
         ("n_refs", C.c_int32),
@@ -130,6 +136,10 @@ def bcio() -> C.CDLL:
     lib.bcio_inflate_blocks.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_int64, C.c_void_p, C.c_uint64, C.c_int]
     lib.bcio_stream_inflate_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.bcio_stream_close.restype = None
+    lib.bcio_stream_set_decoder.argtypes = [C.c_void_p, C.POINTER(BcioDecoder)]
+    lib.bcio_stream_decode_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.bcio_device_handle.argtypes = [C.c_void_p]
+    lib.bcio_device_handle.restype = C.c_void_p
     lib.bcio_find_ref_start.argtypes = [C.c_char_p, C.c_int32, C.POINTER(C.c_uint64)]
     lib.bcio_find_record.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.POINTER(C.c_uint64)]
     lib.bcio_stream_open_range.argtypes = [C.c_char_p, C.c_int, C.c_uint64, C.c_uint64, C.POINTER(C.c_void_p)]

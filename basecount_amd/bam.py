@@ -55,9 +55,18 @@ class Selection:
 
 class BamFile:
     """A fully decoded BAM file (records in file order), or one batch of a BamStream (then its
-    record indices count from the batch's first record, ``first_record`` in the file)."""
+    record indices count from the batch's first record, ``first_record`` in the file).
 
-    def __init__(self, path: str | None, nthreads: int = 0, *, _handle=None, _first: int = 0):
+    A batch of a device-decoding stream (``BamStream(device_decode=ctx)``) has its per-record
+    arrays on the host as usual and ``cigar`` / ``seq`` / ``seq_event`` / ``qual`` in HBM:
+    ``device_arrays`` maps each name to (device pointer, elements), and reading one of those four
+    attributes downloads it once (the fault paths and the pysam-like accessors do).  The device
+    buffers live until ``close()``; ``device_arrays`` is None for a host batch."""
+
+    _LAZY = {"cigar": np.uint32, "seq": np.uint8, "seq_event": np.uint8, "qual": np.uint8}
+
+    def __init__(self, path: str | None, nthreads: int = 0, *, _handle=None, _first: int = 0, _device_ctx=None,
+                 _keep=None):
         lib = N.bcio()
         if _handle is None:
             h = C.c_void_p()
@@ -68,6 +77,7 @@ class BamFile:
         else:
             h = _handle
         self._h = h
+        self._keep = _keep  # a device batch's decoder must outlive it (the close releases through it)
         self.first_record = int(_first)
         nr = lib.bcio_n_refs(h)
         self.references = tuple(lib.bcio_ref_name(h, i).decode() for i in range(nr))
@@ -85,13 +95,45 @@ class BamFile:
         self.qend = _view(r.qend, n, np.int32)
         self.rec_err = _view(r.rec_err, n, np.uint32)
         self.cig_off = _view(r.cig_off, n + 1, np.uint64)
-        self.cigar = _view(r.cigar, int(self.cig_off[-1]) if n else 0, np.uint32)
         self.seq_off = _view(r.seq_off, n + 1, np.uint64)
+        self.ref_span = _view(r.ref_span, n, np.int64)
+        self.device_arrays = None
+        dev = lib.bcio_device_handle(h) if _device_ctx is not None else None
+        if dev:
+            from . import device as D
+
+            a = D.bam_batch_arrays(dev)
+            self._device_ctx = _device_ctx
+            self.device_arrays = {
+                "cigar": (a.cigar or 0, int(self.cig_off[-1]) if n else 0), "seq": (a.seq or 0, int(r.seq_bytes)),
+                "seq_event": (a.seq_event or 0, int(r.seq_event_bytes)),
+                "qual": (a.qual or 0, 2 * int(r.seq_bytes)) if a.qual else None}
+            return  # cigar / seq / seq_event / qual: __getattr__, on first use
+        self.cigar = _view(r.cigar, int(self.cig_off[-1]) if n else 0, np.uint32)
         self.seq = _view(r.seq, int(r.seq_bytes), np.uint8)
         self.qual = _view(r.qual, 2 * int(r.seq_bytes), np.uint8)
-        self.ref_span = _view(r.ref_span, n, np.int64)
         # SEQ in the kernels' BC_SEQ_EVENT layout, padded (uploaded as is: no device pass)
         self.seq_event = _view(r.seq_event, int(r.seq_event_bytes), np.uint8)
+
+    def __getattr__(self, name):
+        # only reached for attributes not set: the device-resident arrays of a device batch
+        dt = BamFile._LAZY.get(name)
+        dev = self.__dict__.get("device_arrays")
+        if dt is None or dev is None:
+            raise AttributeError(name)
+        if dev[name] is None:
+            raise RuntimeError("this batch was decoded without its %s array" % name)
+        if not self.__dict__.get("_h"):
+            raise RuntimeError("the batch is closed: its device arrays are gone")
+        from . import device as D
+
+        ptr, cnt = dev[name]
+        out = np.empty(cnt, dt)
+        if out.nbytes:
+            D.check(D.lib().bc_memcpy_d2h(self._device_ctx.h, out.ctypes.data, ptr, out.nbytes))
+            self._device_ctx.sync()
+        self.__dict__[name] = out
+        return out
 
     def close(self) -> None:
         if getattr(self, "_h", None):
@@ -200,13 +242,19 @@ class BamStream:
     """
 
     def __init__(self, path: str, nthreads: int = 0, *, voff_range: tuple | None = None, device_inflate=None,
-                 inflater: tuple | None = None):
+                 inflater: tuple | None = None, device_decode=None, want_qual: bool = True, seg_bytes: int = 0):
         """``voff_range=(begin, end)``: only the records in [begin, end) (BAM virtual offsets,
         ``find_ref_start``; end None: to the end of the file, begin None: no records).
         ``device_inflate``: a ``device.Context`` whose GPU inflates the stream's BGZF blocks
         (``bc_bgzf_inflate_host`` is handed to the stream as its inflater: no Python on that path;
         a block the device refuses is inflated on the host, so errors are the host's).
-        ``inflater=(fn, user)``: any ``bcio_inflate_fn`` address (or ctypes callback) instead."""
+        ``inflater=(fn, user)``: any ``bcio_inflate_fn`` address (or ctypes callback) instead.
+        ``device_decode``: a ``device.Context`` whose GPU inflates the fills AND decodes their records
+        (``device.BamDecoder``: k_inflate, then bc_bam_index / bc_bam_fill; the inflated bytes stay in
+        HBM and the batches are ``BamFile``s with ``device_arrays``).  A fill the device declines is
+        inflated and decoded on the host, so errors are the host's.  ``want_qual=False`` leaves the
+        batches without a qual array; ``seg_bytes``: the speculation's segment size (0: the default).
+        Range streams keep the host decoder."""
         lib = N.bcio()
         h = C.c_void_p()
         if voff_range is None:
@@ -228,6 +276,16 @@ class BamStream:
             fn, user = inflater
             N.bcio_check(lib.bcio_stream_set_inflater(h, C.cast(fn, C.c_void_p), user))
         self.open_stats = self.inflate_stats()  # the blocks the open itself inflated (the header's)
+        self.decoder = None
+        self._decode_ctx = None
+        if device_decode is not None and voff_range is None:
+            from . import device as D
+
+            self.decoder = D.BamDecoder(device_decode, want_qual, seg_bytes)
+            self._decode_ctx = device_decode
+            user, fill, nxt, pending, release = self.decoder.callbacks()
+            self._decoder_struct = N.BcioDecoder(user, fill, nxt, pending, release)
+            N.bcio_check(lib.bcio_stream_set_decoder(h, C.byref(self._decoder_struct)))
         nr = lib.bcio_stream_n_refs(h)
         self.references = tuple(lib.bcio_stream_ref_name(h, i).decode() for i in range(nr))
         self.lengths = tuple(int(lib.bcio_stream_ref_len(h, i)) for i in range(nr))
@@ -239,7 +297,16 @@ class BamStream:
         N.bcio_check(lib.bcio_stream_next(self._h, int(max_records), C.byref(out)))
         if not out.value:
             return None
-        return BamFile(None, _handle=out, _first=first)
+        return BamFile(None, _handle=out, _first=first, _device_ctx=self._decode_ctx, _keep=self.decoder)
+
+    def decode_stats(self) -> dict:
+        """Fills decoded on the device / on the host while a device decoder was set, and the
+        segments whose speculated entry was wrong and that the device hopped again."""
+        dev, host = C.c_int64(0), C.c_int64(0)
+        if getattr(self, "_h", None):
+            N.bcio_check(N.bcio().bcio_stream_decode_stats(self._h, C.byref(dev), C.byref(host)))
+        rep = self.decoder.stats()["repaired"] if self.decoder is not None and self.decoder.h else 0
+        return {"device": dev.value, "host": host.value, "repaired": rep}
 
     def inflate_stats(self) -> dict:
         """BGZF blocks inflated so far by the stream's inflater ("callback") and on the host."""
@@ -267,6 +334,9 @@ class BamStream:
 
     def close(self) -> None:
         if getattr(self, "_h", None):
+            if getattr(self, "decoder", None) is not None:
+                # (the stream's deletion never calls the decoder; live batches keep it alive)
+                self.decoder.drop()
             N.bcio().bcio_stream_close(self._h)
             self._h = None
 

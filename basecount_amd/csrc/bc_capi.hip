@@ -2,6 +2,7 @@
 // checks, stream/memory management, launch geometry; every count/stat is computed by the
 // kernels in bc_kernels.hip.
 #include <algorithm>
+#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -407,6 +408,364 @@ int bc_bgzf_inflate_host_times(bc_ctx* c, double* ms, int64_t* blocks) {
     if (ms)
         for (int k = 0; k < 3; ++k) ms[k] = c->z_ms[k];
     if (blocks) *blocks = c->z_blocks;
+    return BC_OK;
+}
+
+// ---- BAM record decode (bc_bam.hip) ----
+static_assert(sizeof(bc_bam_batch) == 80, "bc_bam_batch is bc_bam.h's bcb_result");
+
+static int bam_seg_bytes(uint32_t seg_bytes, uint32_t* out) {
+    if (seg_bytes == 0) seg_bytes = BC_BAM_SEG_DEFAULT;
+    if (seg_bytes < 64u || seg_bytes > (1u << 24)) return fail(BC_E_ARG, "bc_bam: seg_bytes must be 0 or 64 .. 2^24");
+    *out = seg_bytes;
+    return BC_OK;
+}
+
+int bc_bam_index_bytes(uint64_t raw_bytes, uint32_t seg_bytes, size_t* bytes) {
+    if (!bytes) return fail(BC_E_ARG, "bc_bam_index_bytes: bytes is NULL");
+    uint32_t seg = 0;
+    if (int rc = bam_seg_bytes(seg_bytes, &seg)) return rc;
+    // a fill too large for the device is declined by bc_bam_index and needs the header only
+    *bytes = raw_bytes > 0x7FFFFFFFull ? 128 : bc::bam_index_bytes(raw_bytes, seg);
+    return BC_OK;
+}
+
+int bc_bam_index(bc_ctx* c, const uint8_t* d_raw, uint64_t raw_bytes, uint64_t first, int64_t max_records, int final,
+                 int32_t n_refs, uint32_t seg_bytes, void* d_work, size_t work_bytes, bc_bam_batch* h_out) {
+    if (!c) return fail(BC_E_ARG, "ctx is NULL");
+    if (!d_raw || !d_work || !h_out) return fail(BC_E_ARG, "bc_bam_index: NULL pointer");
+    if (first > raw_bytes) return fail(BC_E_ARG, "bc_bam_index: first is past raw_bytes");
+    if (max_records < 0) return fail(BC_E_ARG, "bc_bam_index: max_records < 0");
+    if (n_refs < 0) return fail(BC_E_ARG, "bc_bam_index: n_refs < 0");
+    uint32_t seg = 0;
+    if (int rc = bam_seg_bytes(seg_bytes, &seg)) return rc;
+    size_t need = 0;
+    (void)bc_bam_index_bytes(raw_bytes, seg, &need);
+    if (work_bytes < need) return fail(BC_E_ARG, "bc_bam_index: d_work smaller than bc_bam_index_bytes");
+    if ((uintptr_t)d_work & 15u) return fail(BC_E_ARG, "bc_bam_index: d_work must be 16-byte aligned");
+    if (raw_bytes > 0x7FFFFFFFull) {  // declined without touching the device
+        *h_out = bc_bam_batch{};
+        h_out->status = BC_BAM_TOO_LARGE;
+        h_out->used = h_out->err_off = first;
+        h_out->raw_bytes = raw_bytes;
+        h_out->seg_bytes = seg;
+        return BC_OK;
+    }
+    DeviceGuard g(c->device);
+    HIP_TRY(bc::launch_bam_index(c->stream, d_raw, (uint32_t)raw_bytes, seg, (uint32_t)first, max_records, final != 0,
+                                 n_refs, d_work));
+    HIP_TRY(hipMemcpyAsync(h_out, d_work, sizeof *h_out, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return BC_OK;
+}
+
+int bc_bam_fill(bc_ctx* c, const uint8_t* d_raw, const void* d_work, const bc_bam_batch* b, const bc_bam_arrays* o,
+                int want_qual) {
+    if (!c) return fail(BC_E_ARG, "ctx is NULL");
+    if (!d_raw || !d_work || !b || !o) return fail(BC_E_ARG, "bc_bam_fill: NULL pointer");
+    if (b->status != BC_BAM_OK) return fail(BC_E_ARG, "bc_bam_fill: the fill was declined (decode it on the host)");
+    if (b->n < 0 || b->raw_bytes > 0x7FFFFFFFull || b->seg_bytes < 64u || b->seg_bytes > (1u << 24))
+        return fail(BC_E_ARG, "bc_bam_fill: h_batch is not a bc_bam_index result");
+    if (o->n_cap < b->n || o->cigar_cap < b->cigar_words || o->seq_cap < b->seq_bytes)
+        return fail(BC_E_ARG, "bc_bam_fill: the arrays are smaller than the batch");
+    if (!o->tid || !o->pos || !o->flag || !o->mapq || !o->l_seq || !o->qstart || !o->qend || !o->rec_err ||
+        !o->ref_span || !o->cig_off || !o->seq_off || !o->seq_event || (b->cigar_words && !o->cigar))
+        return fail(BC_E_ARG, "bc_bam_fill: missing output array");
+    if (want_qual && !o->qual) return fail(BC_E_ARG, "bc_bam_fill: want_qual needs a qual array");
+    DeviceGuard g(c->device);
+    HIP_TRY(bc::launch_bam_fill(c->stream, d_raw, (uint32_t)b->raw_bytes, (uint32_t)b->seg_bytes, d_work, *o,
+                                want_qual != 0));
+    return BC_OK;
+}
+
+// ---- the stream decoder: fills in, batches out, the inflated bytes stay in HBM ----
+struct bc_bam_decoder {
+    bc_ctx* c = nullptr;
+    bool want_qual = false;
+    uint32_t seg = 0;
+    uint8_t* pend = nullptr;  // inflated bytes; [beg, end) not handed out yet
+    uint64_t beg = 0, end = 0;
+    void* work = nullptr;
+    size_t work_cap = 0;
+    hipEvent_t ev[4] = {};
+    int64_t repaired = 0, declined = 0;
+    double ms[7] = {};
+};
+
+namespace {
+
+struct BamHandle {
+    bc_bam_arrays arrays{};
+    void* slab = nullptr;
+    std::vector<uint8_t> meta;  // the per-record arrays on the host
+};
+
+constexpr size_t kBamAlign = 256;
+size_t bam_up(size_t v) { return (v + kBamAlign - 1) / kBamAlign * kBamAlign; }
+
+// host wall time of one decoder call into ms[slot]
+struct BamWall {
+    bc_bam_decoder* d;
+    int slot;
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    ~BamWall() { d->ms[slot] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+};
+
+void bam_elapsed(bc_bam_decoder* d, int slot, int a, int b) {
+    float t = 0.f;
+    if (hipEventElapsedTime(&t, d->ev[a], d->ev[b]) == hipSuccess) d->ms[slot] += t;
+}
+
+}  // namespace
+
+int bc_bam_decoder_create(bc_ctx* c, int want_qual, uint32_t seg_bytes, bc_bam_decoder** out) {
+    if (!c || !out) return fail(BC_E_ARG, "bc_bam_decoder_create: NULL argument");
+    uint32_t seg = 0;
+    if (int rc = bam_seg_bytes(seg_bytes, &seg)) return rc;
+    DeviceGuard g(c->device);
+    auto* d = new bc_bam_decoder();
+    d->c = c;
+    d->want_qual = want_qual != 0;
+    d->seg = seg;
+    for (auto& e : d->ev) {
+        hipError_t err = hipEventCreate(&e);
+        if (err != hipSuccess) {
+            (void)bc_bam_decoder_destroy(d);
+            return hip_fail(err, "hipEventCreate");
+        }
+    }
+    *out = d;
+    return BC_OK;
+}
+
+int bc_bam_decoder_destroy(bc_bam_decoder* d) {
+    if (!d) return fail(BC_E_ARG, "decoder is NULL");
+    DeviceGuard g(d->c->device);
+    (void)hipStreamSynchronize(d->c->stream);
+    if (d->pend) (void)hipFree(d->pend);
+    if (d->work) (void)hipFree(d->work);
+    for (auto& e : d->ev)
+        if (e) (void)hipEventDestroy(e);
+    delete d;
+    return BC_OK;
+}
+
+int bc_bam_decoder_fill(void* user, int append, const uint8_t* h_carry, uint64_t carry_bytes, const uint8_t* h_comp,
+                        uint64_t comp_bytes, const bc_zblock* h_blocks, int64_t n, uint64_t inflated) {
+    auto* d = static_cast<bc_bam_decoder*>(user);
+    if (!d) return fail(BC_E_ARG, "decoder is NULL");
+    if (n < 0 || (n > 0 && (!h_comp || !h_blocks)) || (!append && carry_bytes && !h_carry))
+        return fail(BC_E_ARG, "bc_bam_decoder_fill: bad argument");
+    bc_ctx* c = d->c;
+    BamWall wall{d, 5};
+    const uint64_t keep = append ? d->end - d->beg : carry_bytes;
+    if (keep + inflated > 0x7FFFFFFFull) return (++d->declined, 1);  // 32-bit offsets on the device
+    // the descriptors for the device: the compressed span as it lies in the file, the output behind
+    // the kept bytes; one the host can already refuse declines the fill
+    std::vector<bc_zblock> dev((size_t)n);
+    uint64_t cmin = UINT64_MAX, cmax = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        const bc_zblock& z = h_blocks[i];
+        if (z.isize > 65536u || z.coff > comp_bytes || z.clen > comp_bytes - z.coff || z.uoff > inflated ||
+            z.isize > inflated - z.uoff)
+            return (++d->declined, 1);
+        cmin = std::min(cmin, z.coff);
+        cmax = std::max(cmax, z.coff + z.clen);
+        dev[(size_t)i] = z;
+    }
+    if (cmin > cmax) cmin = cmax = 0;
+    for (auto& z : dev) {
+        z.coff -= cmin;
+        z.uoff += keep;
+    }
+    const uint64_t span = cmax - cmin, total = keep + inflated;
+    std::lock_guard<std::mutex> lock(c->z_mutex);
+    DeviceGuard g(c->device);
+    int rc;
+    if ((rc = z_reserve(c, 0, span + 16)) != BC_OK || (rc = z_reserve(c, 1, (size_t)n * sizeof(bc_zblock) + 16)) != BC_OK ||
+        (rc = z_reserve(c, 3, (size_t)n + 16)) != BC_OK)
+        return rc;
+    uint8_t* nb = nullptr;
+    HIP_TRY(hipMalloc((void**)&nb, total + 64));
+    std::vector<uint8_t> status((size_t)n, 1);
+    hipError_t e = hipEventRecord(d->ev[0], c->stream);
+    if (e == hipSuccess && keep)
+        e = append ? hipMemcpyAsync(nb, d->pend + d->beg, keep, hipMemcpyDeviceToDevice, c->stream)
+                   : hipMemcpyAsync(nb, h_carry, keep, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && span) e = hipMemcpyAsync(c->z_buf[0], h_comp + cmin, span, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && n)
+        e = hipMemcpyAsync(c->z_buf[1], dev.data(), (size_t)n * sizeof(bc_zblock), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipEventRecord(d->ev[1], c->stream);
+    if (e == hipSuccess)
+        e = bc::launch_inflate(c->stream, static_cast<uint8_t*>(c->z_buf[0]), span, static_cast<bc_zblock*>(c->z_buf[1]), n,
+                               nb, total, static_cast<uint8_t*>(c->z_buf[3]));
+    if (e == hipSuccess) e = hipEventRecord(d->ev[2], c->stream);
+    if (e == hipSuccess && n) e = hipMemcpyAsync(status.data(), c->z_buf[3], (size_t)n, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipEventRecord(d->ev[3], c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        (void)hipFree(nb);
+        return hip_fail(e, "bc_bam_decoder_fill");
+    }
+    bam_elapsed(d, 0, 0, 1);
+    bam_elapsed(d, 1, 1, 2);
+    bam_elapsed(d, 4, 2, 3);
+    for (uint8_t st : status)
+        if (st != 0) {  // a block k_inflate refuses: the host inflates and decodes this fill
+            (void)hipFree(nb);
+            return (++d->declined, 1);
+        }
+    if (d->pend) (void)hipFree(d->pend);
+    d->pend = nb;
+    d->beg = 0;
+    d->end = total;
+    return BC_OK;
+}
+
+int bc_bam_decoder_next(void* user, int64_t max_records, int final, int32_t n_refs, bc_bam_host_batch* out) {
+    auto* d = static_cast<bc_bam_decoder*>(user);
+    if (!d || !out) return fail(BC_E_ARG, "bc_bam_decoder_next: NULL argument");
+    if (max_records < 0 || n_refs < 0) return fail(BC_E_ARG, "bc_bam_decoder_next: negative argument");
+    *out = bc_bam_host_batch{};
+    bc_ctx* c = d->c;
+    BamWall wall{d, 6};
+    const uint64_t N = d->end - d->beg;
+    if (!d->pend || N == 0) return final ? 0 : 1;
+    DeviceGuard g(c->device);
+    size_t need = 0;
+    if (int rc = bc_bam_index_bytes(N, d->seg, &need)) return rc;
+    if (need > d->work_cap) {
+        if (d->work) {
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            HIP_TRY(hipFree(d->work));
+            d->work = nullptr;
+            d->work_cap = 0;
+        }
+        HIP_TRY(hipMalloc(&d->work, need + need / 4));
+        d->work_cap = need + need / 4;
+    }
+    const uint8_t* raw = d->pend + d->beg;
+    bc_bam_batch b{};
+    HIP_TRY(hipEventRecord(d->ev[0], c->stream));
+    if (int rc = bc_bam_index(c, raw, N, 0, max_records, final, n_refs, d->seg, d->work, d->work_cap, &b)) return rc;
+    HIP_TRY(hipEventRecord(d->ev[1], c->stream));
+    HIP_TRY(hipEventSynchronize(d->ev[1]));
+    bam_elapsed(d, 2, 0, 1);
+    d->repaired += b.repaired;
+    if (b.status != BC_BAM_OK) return (++d->declined, 2);
+    out->n = b.n;
+    if (!final && b.n < max_records) return 1;  // more bytes first; nothing consumed
+    if (b.n == 0) return 0;
+    // one allocation: the per-record arrays in front (one download), then the batch's bytes
+    const size_t n = (size_t)b.n, cw = (size_t)b.cigar_words, sb = (size_t)b.seq_bytes;
+    const size_t sizes[15] = {4 * n, 4 * n, 2 * n, n, 4 * n, 4 * n, 4 * n, 4 * n, 8 * n, 8 * (n + 1), 8 * (n + 1),
+                              4 * cw, sb, bc::seq_event_bytes((int64_t)sb), d->want_qual ? 2 * sb : 0};
+    size_t off[16] = {0};
+    for (int i = 0; i < 15; ++i) off[i + 1] = off[i] + bam_up(sizes[i]);
+    auto h = std::make_unique<BamHandle>();
+    HIP_TRY(hipMalloc(&h->slab, off[15] + kBamAlign));
+    uint8_t* p = static_cast<uint8_t*>(h->slab);
+    bc_bam_arrays& a = h->arrays;
+    a.tid = (int32_t*)(p + off[0]);
+    a.pos = (int32_t*)(p + off[1]);
+    a.flag = (uint16_t*)(p + off[2]);
+    a.mapq = p + off[3];
+    a.l_seq = (int32_t*)(p + off[4]);
+    a.qstart = (int32_t*)(p + off[5]);
+    a.qend = (int32_t*)(p + off[6]);
+    a.rec_err = (uint32_t*)(p + off[7]);
+    a.ref_span = (int64_t*)(p + off[8]);
+    a.cig_off = (uint64_t*)(p + off[9]);
+    a.seq_off = (uint64_t*)(p + off[10]);
+    a.cigar = (uint32_t*)(p + off[11]);
+    a.seq = p + off[12];
+    a.seq_event = p + off[13];
+    a.qual = d->want_qual ? p + off[14] : nullptr;
+    a.n_cap = b.n;
+    a.cigar_cap = b.cigar_words;
+    a.seq_cap = b.seq_bytes;
+    h->meta.resize(off[11]);
+    hipError_t e = hipEventRecord(d->ev[1], c->stream);
+    int rc = BC_OK;
+    if (e == hipSuccess) rc = bc_bam_fill(c, raw, d->work, &b, &a, d->want_qual ? 1 : 0);
+    if (rc == BC_OK && e == hipSuccess) e = hipEventRecord(d->ev[2], c->stream);
+    if (rc == BC_OK && e == hipSuccess) e = hipMemcpyAsync(h->meta.data(), p, off[11], hipMemcpyDeviceToHost, c->stream);
+    if (rc == BC_OK && e == hipSuccess) e = hipEventRecord(d->ev[3], c->stream);
+    if (rc == BC_OK && e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (rc != BC_OK || e != hipSuccess) {
+        (void)hipFree(h->slab);
+        return rc != BC_OK ? rc : hip_fail(e, "bc_bam_decoder_next");
+    }
+    bam_elapsed(d, 3, 1, 2);
+    bam_elapsed(d, 4, 2, 3);
+    const uint8_t* m = h->meta.data();
+    out->used = b.used;
+    out->cigar_words = b.cigar_words;
+    out->seq_bytes = b.seq_bytes;
+    out->tid = (const int32_t*)(m + off[0]);
+    out->pos = (const int32_t*)(m + off[1]);
+    out->flag = (const uint16_t*)(m + off[2]);
+    out->mapq = m + off[3];
+    out->l_seq = (const int32_t*)(m + off[4]);
+    out->qstart = (const int32_t*)(m + off[5]);
+    out->qend = (const int32_t*)(m + off[6]);
+    out->rec_err = (const uint32_t*)(m + off[7]);
+    out->ref_span = (const int64_t*)(m + off[8]);
+    out->cig_off = (const uint64_t*)(m + off[9]);
+    out->seq_off = (const uint64_t*)(m + off[10]);
+    d->beg += b.used;
+    out->handle = h.release();
+    return 0;
+}
+
+int bc_bam_decoder_pending(void* user, uint8_t* h_dst, uint64_t* bytes) {
+    auto* d = static_cast<bc_bam_decoder*>(user);
+    if (!d || !bytes) return fail(BC_E_ARG, "bc_bam_decoder_pending: NULL argument");
+    *bytes = d->end - d->beg;
+    if (!h_dst) return BC_OK;
+    DeviceGuard g(d->c->device);
+    if (*bytes) {
+        HIP_TRY(hipMemcpyAsync(h_dst, d->pend + d->beg, *bytes, hipMemcpyDeviceToHost, d->c->stream));
+        HIP_TRY(hipStreamSynchronize(d->c->stream));
+    }
+    if (d->pend) (void)hipFree(d->pend);
+    d->pend = nullptr;
+    d->beg = d->end = 0;
+    return BC_OK;
+}
+
+int bc_bam_decoder_drop(bc_bam_decoder* d) {
+    if (!d) return fail(BC_E_ARG, "decoder is NULL");
+    DeviceGuard g(d->c->device);
+    if (d->pend) HIP_TRY(hipFree(d->pend));
+    d->pend = nullptr;
+    d->beg = d->end = 0;
+    return BC_OK;
+}
+
+void bc_bam_decoder_release(void* user, void* handle) {
+    auto* d = static_cast<bc_bam_decoder*>(user);
+    auto* h = static_cast<BamHandle*>(handle);
+    if (!h) return;
+    if (d) {
+        DeviceGuard g(d->c->device);
+        if (h->slab) (void)hipFree(h->slab);
+    }
+    delete h;
+}
+
+int bc_bam_batch_arrays(const void* handle, bc_bam_arrays* out) {
+    if (!handle || !out) return fail(BC_E_ARG, "bc_bam_batch_arrays: NULL argument");
+    *out = static_cast<const BamHandle*>(handle)->arrays;
+    return BC_OK;
+}
+
+int bc_bam_decoder_stats(bc_bam_decoder* d, int64_t* repaired, int64_t* declined, double* ms) {
+    if (!d) return fail(BC_E_ARG, "decoder is NULL");
+    if (repaired) *repaired = d->repaired;
+    if (declined) *declined = d->declined;
+    if (ms)
+        for (int k = 0; k < 7; ++k) ms[k] = d->ms[k];
     return BC_OK;
 }
 

@@ -202,4 +202,11 @@ hipError_t launch_sum_segments(hipStream_t s, int n_seg, const int64_t* ref_len,
 hipError_t launch_inflate(hipStream_t s, const uint8_t* comp, uint64_t comp_bytes, const bc_zblock* blocks, int64_t n,
                           uint8_t* out, uint64_t out_bytes, uint8_t* status);
 
+// ---- BAM record decode (bc_bam.hip over bc_bam.h): raw_bytes < 2^31 is the caller's check ----
+size_t bam_index_bytes(uint64_t raw_bytes, uint64_t seg_bytes);
+hipError_t launch_bam_index(hipStream_t s, const uint8_t* raw, uint32_t N, uint32_t seg_bytes, uint32_t first,
+                            int64_t max_records, bool final, int32_t n_refs, void* work);
+hipError_t launch_bam_fill(hipStream_t s, const uint8_t* raw, uint32_t N, uint32_t seg_bytes, const void* work,
+                           const bc_bam_arrays& out, bool want_qual);
+
 }  // namespace bc

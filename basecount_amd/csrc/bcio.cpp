@@ -245,6 +245,14 @@ struct bcio_file {
         uvec<uint32_t> cig_beg, cig_n, seq_nib, qlen;
     };
     std::vector<std::unique_ptr<Sel>> sels;
+    // a batch of a stream's decoder (bcio_stream_set_decoder): cigar / seq / qual / seq_ev stay
+    // empty, the handle owns them and is released with the batch
+    void* dev_handle = nullptr;
+    void* dev_user = nullptr;
+    void (*dev_release)(void*, void*) = nullptr;
+    ~bcio_file() {
+        if (dev_handle && dev_release) dev_release(dev_user, dev_handle);
+    }
 };
 
 extern "C" const char* bcio_last_error(void) { return g_err.c_str(); }
@@ -663,8 +671,14 @@ extern "C" int bcio_open(const char* path, int nthreads, bcio_file** out) {
 
 // Returning a few hundred MB of decoded arrays to the kernel takes tens of ms; nothing waits for
 // it, so it happens on a detached thread (synchronously if a thread cannot be started).
+extern "C" void* bcio_device_handle(const bcio_file* f) { return f ? f->dev_handle : nullptr; }
+
 extern "C" void bcio_close(bcio_file* f) {
     if (!f) return;
+    if (f->dev_handle) {  // device memory goes back in the caller's thread, in order with its other calls
+        delete f;
+        return;
+    }
     try {
         std::thread([f] { delete f; }).detach();
     } catch (...) {
@@ -698,7 +712,8 @@ extern "C" int bcio_get_records(const bcio_file* f, bcio_records* o) {
     o->seq_bytes = f->seq_off.empty() ? 0 : f->seq_off.back();
     o->ref_span = f->ref_span.data();
     o->seq_event = f->seq_ev.data();
-    o->seq_event_bytes = (uint64_t)f->seq_ev.size();
+    o->seq_event_bytes = f->dev_handle ? seq_event_bytes(o->seq_bytes) : (uint64_t)f->seq_ev.size();
+    if (f->dev_handle) o->cigar = nullptr, o->seq = o->qual = o->seq_event = nullptr;
     return BCIO_OK;
 }
 
@@ -832,6 +847,11 @@ struct bcio_stream {
     bcio_inflate_fn inflater = nullptr;
     void* inflater_user = nullptr;
     int64_t by_callback = 0, by_host = 0;
+    // bcio_stream_set_decoder: while dev_pending the bytes not handed out yet are the decoder's
+    // (pend is empty); otherwise they are pend's as without a decoder
+    bcio_decoder dec{};
+    bool has_dec = false, dev_pending = false;
+    int64_t dev_fills = 0, host_fills = 0;
     bool all_read() const { return coff >= std::min<uint64_t>(cend, file.size()); }
     const uint8_t* base() const { return pend ? pend->data() + pbeg : nullptr; }
     uint64_t avail() const { return pend_n - pbeg; }
@@ -839,11 +859,16 @@ struct bcio_stream {
 
 namespace {
 
-// scan + inflate blocks from coff until they hold >= want inflated bytes (or the file ends)
-int stream_fill(bcio_stream* s, uint64_t want) {
+// the blocks from coff on that hold >= want inflated bytes (or up to the file's end)
+struct Scan {
+    std::vector<Block> blocks;
+    uint64_t off = 0, uoff = 0, trim = 0;
+};
+
+int stream_scan(bcio_stream* s, uint64_t want, Scan& sc) {
     const uint8_t* comp = s->file.data();
     const uint64_t n = s->file.size();
-    std::vector<Block> blocks;
+    std::vector<Block>& blocks = sc.blocks;
     uint64_t off = s->coff, uoff = 0, trim = 0;
     const uint64_t lim = std::min<uint64_t>(n, s->cend);
     while (off < lim && uoff < want) {
@@ -862,6 +887,28 @@ int stream_fill(bcio_stream* s, uint64_t want) {
         }
         off += bsize;
     }
+    sc.off = off;
+    sc.uoff = uoff;
+    sc.trim = trim;
+    return BCIO_OK;
+}
+
+void stream_advance(bcio_stream* s, uint64_t off) {
+    s->coff = off;
+    // give the consumed compressed pages back (whole pages below the next block)
+    const uint64_t page = 4096, upto = off / page * page;
+    if (upto > s->dropped) {
+        s->file.drop(s->dropped, upto - s->dropped);
+        s->dropped = upto;
+    }
+}
+
+// inflate the scanned blocks behind the bytes not handed out yet (the inflater first, if any)
+int stream_inflate(bcio_stream* s, const Scan& sc) {
+    const uint8_t* comp = s->file.data();
+    const uint64_t n = s->file.size();
+    const std::vector<Block>& blocks = sc.blocks;
+    const uint64_t off = sc.off, uoff = sc.uoff, trim = sc.trim;
     // one buffer: the bytes not handed out yet, then the new blocks' bytes
     const uint64_t keep = s->avail();
     auto next = std::make_unique<MapBuf>(keep + uoff + 64);
@@ -894,14 +941,125 @@ int stream_fill(bcio_stream* s, uint64_t want) {
     s->pend = std::move(next);
     s->pend_n = keep + uoff - trim;
     s->pbeg = 0;
-    s->coff = off;
-    // give the consumed compressed pages back (whole pages below the next block)
-    const uint64_t page = 4096, upto = off / page * page;
-    if (upto > s->dropped) {
-        s->file.drop(s->dropped, upto - s->dropped);
-        s->dropped = upto;
+    stream_advance(s, off);
+    return BCIO_OK;
+}
+
+// scan + inflate blocks from coff until they hold >= want inflated bytes (or the file ends)
+int stream_fill(bcio_stream* s, uint64_t want) {
+    Scan sc;
+    int rc = stream_scan(s, want, sc);
+    if (rc != BCIO_OK) return rc;
+    return stream_inflate(s, sc);
+}
+
+// the decoder's pending bytes back into pend: the host decodes them
+int stream_pull(bcio_stream* s) {
+    uint64_t bytes = 0;
+    if (s->dec.pending(s->dec.user, nullptr, &bytes) != 0) return fail(BCIO_E_IO, "decoder: pending bytes lost");
+    auto buf = std::make_unique<MapBuf>(bytes + 64);
+    if (!buf->ok()) return fail(BCIO_E_IO, "cannot allocate the inflate buffer");
+    if (s->dec.pending(s->dec.user, buf->data(), &bytes) != 0) return fail(BCIO_E_IO, "decoder: pending bytes lost");
+    s->pend = std::move(buf);
+    s->pend_n = bytes;
+    s->pbeg = 0;
+    s->dev_pending = false;
+    if (s->dev_fills > 0) {  // the fill those bytes came with is the host's after all
+        --s->dev_fills;
+        ++s->host_fills;
     }
     return BCIO_OK;
+}
+
+// A fill handed to the decoder.  BCIO_OK: the decoder holds the pending bytes; 1: it declined and
+// the fill is pend's, inflated as without a decoder; < 0: error.
+int stream_fill_device(bcio_stream* s, uint64_t want) {
+    Scan sc;
+    int rc = stream_scan(s, want, sc);
+    if (rc != BCIO_OK) return rc;
+    std::vector<bcio_zblock> zb(sc.blocks.size());
+    for (size_t i = 0; i < zb.size(); ++i)
+        zb[i] = bcio_zblock{sc.blocks[i].coff, (uint32_t)sc.blocks[i].clen, sc.blocks[i].isize, sc.blocks[i].uoff};
+    const bool host_carry = !s->dev_pending;
+    if (s->dec.fill(s->dec.user, host_carry ? 0 : 1, host_carry ? s->base() : nullptr, host_carry ? s->avail() : 0,
+                    s->file.data(), s->file.size(), zb.data(), (int64_t)zb.size(), sc.uoff) == 0) {
+        s->pend.reset();
+        s->pend_n = s->pbeg = 0;
+        s->dev_pending = true;
+        ++s->dev_fills;
+        s->by_callback += (int64_t)sc.blocks.size();
+        stream_advance(s, sc.off);
+        return BCIO_OK;
+    }
+    if (s->dev_pending && (rc = stream_pull(s)) != BCIO_OK) return rc;
+    ++s->host_fills;
+    if ((rc = stream_inflate(s, sc)) != BCIO_OK) return rc;
+    return 1;
+}
+
+// the bytes a fill should bring for `missing` more records of `per` bytes each, at least 8 MiB
+uint64_t fill_want(double per, int64_t missing) {
+    const double need = per * (double)missing * 1.05 + 65536.0;
+    return (uint64_t)std::min(std::max(need, 8.0 * (1 << 20)), 8.0 * (1ull << 30));
+}
+
+template <class T>
+void adopt(uvec<T>& v, const T* p, size_t n) {
+    v.resize(n);
+    if (n) std::memcpy(v.data(), p, n * sizeof(T));
+}
+
+// The next batch from the stream's decoder.  BCIO_OK with *done: *out is the batch (or NULL at the
+// end of the file); BCIO_OK without: the pending bytes are pend's, the host decodes.
+int stream_next_device(bcio_stream* s, int64_t max_records, bcio_file** out, bool* done) {
+    *done = false;
+    for (;;) {
+        const double per = s->rec_bytes > 0 ? s->rec_bytes : 512.0;
+        if (!s->dev_pending) {
+            if (s->all_read() && s->avail() == 0) return BCIO_OK;  // the end of the file: the host says so
+            // (at the file's end the fill has no blocks: the carried bytes alone)
+            const int rc = stream_fill_device(s, fill_want(per, max_records));
+            if (rc < 0) return rc;
+            if (rc == 1) return BCIO_OK;
+            continue;
+        }
+        bcio_dev_batch b{};
+        const int st = s->dec.next(s->dec.user, max_records, s->all_read() ? 1 : 0, (int32_t)s->names.size(), &b);
+        if (st == 1 && !s->all_read()) {
+            const int rc = stream_fill_device(s, fill_want(per, max_records - b.n));
+            if (rc < 0) return rc;
+            if (rc == 1) return BCIO_OK;
+            continue;
+        }
+        if (st != 0) return stream_pull(s);  // declined
+        *done = true;
+        if (b.n == 0) {
+            if (b.handle) s->dec.release(s->dec.user, b.handle);
+            return BCIO_OK;  // end of file
+        }
+        auto* f = new bcio_file();
+        f->names = s->names;
+        f->lens = s->lens;
+        const size_t n = (size_t)b.n;
+        adopt(f->tid, b.tid, n);
+        adopt(f->pos, b.pos, n);
+        adopt(f->flag, b.flag, n);
+        adopt(f->mapq, b.mapq, n);
+        adopt(f->l_seq, b.l_seq, n);
+        adopt(f->qstart, b.qstart, n);
+        adopt(f->qend, b.qend, n);
+        adopt(f->rec_err, b.rec_err, n);
+        adopt(f->ref_span, b.ref_span, n);
+        adopt(f->cig_off, b.cig_off, n + 1);
+        adopt(f->seq_off, b.seq_off, n + 1);
+        f->dev_handle = b.handle;
+        f->dev_user = s->dec.user;
+        f->dev_release = s->dec.release;
+        s->rec_bytes = (double)b.used / (double)b.n;
+        s->returned += b.n;
+        *out = f;
+        return BCIO_OK;
+    }
 }
 
 void hop_reset(Hop& h) {
@@ -946,6 +1104,25 @@ extern "C" int bcio_stream_set_inflater(bcio_stream* s, bcio_inflate_fn fn, void
     return BCIO_OK;
 }
 
+extern "C" int bcio_stream_set_decoder(bcio_stream* s, const bcio_decoder* d) {
+    if (!s) return fail(BCIO_E_ARG, "null argument");
+    if (d && (!d->fill || !d->next || !d->pending || !d->release)) return fail(BCIO_E_ARG, "decoder: null callback");
+    if (s->dev_pending) {  // the old decoder's pending bytes come back to the host first
+        int rc = stream_pull(s);
+        if (rc != BCIO_OK) return rc;
+    }
+    s->has_dec = d != nullptr && s->cend == UINT64_MAX;  // range streams keep the host decoder
+    s->dec = d ? *d : bcio_decoder{};
+    return BCIO_OK;
+}
+
+extern "C" int bcio_stream_decode_stats(const bcio_stream* s, int64_t* by_decoder, int64_t* by_host) {
+    if (!s) return fail(BCIO_E_ARG, "null argument");
+    if (by_decoder) *by_decoder = s->dev_fills;
+    if (by_host) *by_host = s->host_fills;
+    return BCIO_OK;
+}
+
 extern "C" int bcio_stream_inflate_stats(const bcio_stream* s, int64_t* blocks_by_callback, int64_t* blocks_by_host) {
     if (!s) return fail(BCIO_E_ARG, "null argument");
     if (blocks_by_callback) *blocks_by_callback = s->by_callback;
@@ -970,6 +1147,11 @@ extern "C" int bcio_inflate_blocks(const uint8_t* comp, uint64_t comp_bytes, con
 extern "C" int bcio_stream_next(bcio_stream* s, int64_t max_records, bcio_file** out) {
     if (!s || !out || max_records <= 0) return fail(BCIO_E_ARG, "bad argument");
     *out = nullptr;
+    if (s->has_dec) {
+        bool done = false;
+        int rc = stream_next_device(s, max_records, out, &done);
+        if (rc != BCIO_OK || done) return rc;
+    }
     // the hop over the next batch's records, continued after each fill (each byte hopped once)
     Hop& h = s->hop;
     for (;;) {
@@ -979,9 +1161,8 @@ extern "C" int bcio_stream_next(bcio_stream* s, int64_t max_records, bcio_file**
         if (m >= max_records || s->all_read()) break;
         // the bytes the missing records should take (mean record size so far), at least 8 MiB
         const double per = m > 0 ? (double)h.q / (double)m : (s->rec_bytes > 0 ? s->rec_bytes : 512.0);
-        const double need = per * (double)(max_records - m) * 1.05 + 65536.0;
-        const uint64_t want = (uint64_t)std::min(std::max(need, 8.0 * (1 << 20)), 8.0 * (1ull << 30));
-        if ((rc = stream_fill(s, want)) != BCIO_OK) return rc;
+        if (s->has_dec) ++s->host_fills;
+        if ((rc = stream_fill(s, fill_want(per, max_records - m))) != BCIO_OK) return rc;
     }
     if (h.starts.empty()) {
         if (s->avail())  // bytes left that never make a whole record

@@ -53,6 +53,34 @@ class BcZBlock(C.Structure):
     _fields_ = [("coff", C.c_uint64), ("clen", C.c_uint32), ("isize", C.c_uint32), ("uoff", C.c_uint64)]
 
 
+class BcBamBatch(C.Structure):
+    """bc_bam_batch: what bc_bam_index found (status != 0: the fill is declined)."""
+    _fields_ = [("n", C.c_int64), ("used", C.c_uint64), ("cigar_words", C.c_uint64), ("seq_bytes", C.c_uint64),
+                ("status", C.c_int32), ("reserved", C.c_int32), ("err_off", C.c_uint64), ("segments", C.c_int64),
+                ("repaired", C.c_int64), ("raw_bytes", C.c_uint64), ("seg_bytes", C.c_uint64)]
+
+
+# bc_bam_arrays' device arrays: name, element type, elements for (n, cigar_words, seq_bytes)
+BAM_ARRAYS = (
+    ("tid", np.int32, lambda n, cw, sb: n), ("pos", np.int32, lambda n, cw, sb: n),
+    ("flag", np.uint16, lambda n, cw, sb: n), ("mapq", np.uint8, lambda n, cw, sb: n),
+    ("l_seq", np.int32, lambda n, cw, sb: n), ("qstart", np.int32, lambda n, cw, sb: n),
+    ("qend", np.int32, lambda n, cw, sb: n), ("rec_err", np.uint32, lambda n, cw, sb: n),
+    ("ref_span", np.int64, lambda n, cw, sb: n), ("cig_off", np.uint64, lambda n, cw, sb: n + 1),
+    ("seq_off", np.uint64, lambda n, cw, sb: n + 1), ("cigar", np.uint32, lambda n, cw, sb: cw),
+    ("seq", np.uint8, lambda n, cw, sb: sb), ("seq_event", np.uint8, lambda n, cw, sb: seq_event_bytes(sb)),
+    ("qual", np.uint8, lambda n, cw, sb: 2 * sb),
+)
+
+
+class BcBamArrays(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name, _, _ in BAM_ARRAYS] + [
+        ("n_cap", C.c_int64), ("cigar_cap", C.c_uint64), ("seq_cap", C.c_uint64)]
+
+
+BAM_STATUS = ("ok", "partial_len", "partial", "short", "neg_lseq", "fields", "too_large", "repairs", "internal")  # BC_BAM_*
+
+
 ZBLOCK_DTYPE = np.dtype([("coff", "<u8"), ("clen", "<u4"), ("isize", "<u4"), ("uoff", "<u8")])  # 24 bytes
 
 
@@ -143,6 +171,16 @@ def lib() -> C.CDLL:
         "bc_bgzf_inflate": ([vp, vp, C.c_uint64, vp, i64, vp, C.c_uint64, vp], C.c_int),
         "bc_bgzf_inflate_host": ([vp, vp, C.c_uint64, vp, i64, vp, C.c_uint64, vp], C.c_int),
         "bc_bgzf_inflate_host_times": ([vp, C.POINTER(dbl * 3), C.POINTER(i64)], C.c_int),
+        # BAM record decode on the device (bc_bam.hip)
+        "bc_bam_index_bytes": ([C.c_uint64, u32, C.POINTER(C.c_size_t)], C.c_int),
+        "bc_bam_index": ([vp, vp, C.c_uint64, C.c_uint64, i64, C.c_int, C.c_int32, u32, vp, C.c_size_t,
+                          C.POINTER(BcBamBatch)], C.c_int),
+        "bc_bam_fill": ([vp, vp, vp, C.POINTER(BcBamBatch), C.POINTER(BcBamArrays), C.c_int], C.c_int),
+        "bc_bam_decoder_create": ([vp, C.c_int, u32, C.POINTER(vp)], C.c_int),
+        "bc_bam_decoder_destroy": ([vp], C.c_int),
+        "bc_bam_batch_arrays": ([vp, C.POINTER(BcBamArrays)], C.c_int),
+        "bc_bam_decoder_stats": ([vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(dbl * 7)], C.c_int),
+        "bc_bam_decoder_drop": ([vp], C.c_int),
         # multi-GPU (bc_comm.hip)
         "bc_comm_unique_id": ([vp], C.c_int),
         "bc_comm_init": ([vp, vp, C.c_int, C.c_int, C.POINTER(vp)], C.c_int),
@@ -446,6 +484,37 @@ class Context:
         bc_bgzf_inflate_host, so no Python runs on the stream's fill path."""
         return C.cast(lib().bc_bgzf_inflate_host, C.c_void_p).value, self.h
 
+    # BAM record decode on the device (bc_bam.hip) --------------------------------------------
+    def bam_index(self, d_raw: int, raw_bytes: int, first: int, max_records: int, final: bool, n_refs: int,
+                  d_work: int, work_bytes: int, seg_bytes: int = 0) -> BcBamBatch:
+        """bc_bam_index: the record chain of d_raw[first, raw_bytes) into d_work (blocking: it
+        returns the counts that size the arrays).  A non-zero ``status`` declines the fill."""
+        b = BcBamBatch()
+        check(lib().bc_bam_index(self.h, d_raw, int(raw_bytes), int(first), int(max_records), int(bool(final)),
+                                 int(n_refs), int(seg_bytes), d_work, int(work_bytes), C.byref(b)))
+        return b
+
+    def bam_fill(self, d_raw: int, d_work: int, batch: BcBamBatch, arrays: BcBamArrays, want_qual: bool) -> None:
+        """bc_bam_fill: the indexed batch's arrays, stream-ordered (capturable, no allocation)."""
+        check(lib().bc_bam_fill(self.h, d_raw, d_work, C.byref(batch), C.byref(arrays), int(bool(want_qual))))
+
+    def bam_decode(self, d_raw: int, raw_bytes: int, first: int, max_records: int, final: bool, n_refs: int,
+                   want_qual: bool = True, seg_bytes: int = 0):
+        """Index and fill one batch into fresh device buffers: a DeviceBamBatch, or None with the
+        declining BcBamBatch when the device declines the fill ((batch, None): decode it on the
+        host).  ``max_records`` < 0: no limit."""
+        work = self.alloc(bam_index_bytes(raw_bytes, seg_bytes))
+        lim = (1 << 63) - 1 if max_records < 0 else int(max_records)
+        b = self.bam_index(d_raw, raw_bytes, first, lim, final, n_refs, work.ptr, work.nbytes, seg_bytes)
+        if b.status != 0:
+            work.free()
+            return b, None
+        out = DeviceBamBatch(self, b, want_qual)
+        self.bam_fill(d_raw, work.ptr, b, out.arrays, want_qual)
+        self.sync()  # the work buffer is released here; the arrays are complete
+        work.free()
+        return b, out
+
     def capture(self, fn) -> "Graph":
         """Record the compute calls made by fn() into a hipGraph (replay with Graph.launch)."""
         check(lib().bc_graph_begin(self.h))
@@ -526,6 +595,91 @@ class Graph:
                 self.h = None
         except Exception:
             pass
+
+
+class BamDecoder:
+    """bc_bam_decoder: a stream's record decoder on this context's GPU (bam.BamStream(device_decode=...)
+    hands its four C callbacks to the stream, so no Python runs between a fill and its batches)."""
+
+    def __init__(self, ctx: "Context", want_qual: bool = True, seg_bytes: int = 0):
+        self.ctx = ctx
+        h = C.c_void_p()
+        check(lib().bc_bam_decoder_create(ctx.h, int(bool(want_qual)), int(seg_bytes), C.byref(h)))
+        self.h = h.value
+        self.want_qual = bool(want_qual)
+
+    def callbacks(self) -> tuple:
+        """(user, fill, next, pending, release) addresses for bcio_decoder."""
+        L = lib()
+        return (self.h,) + tuple(C.cast(getattr(L, "bc_bam_decoder_" + n), C.c_void_p).value
+                                 for n in ("fill", "next", "pending", "release"))
+
+    def stats(self) -> dict:
+        rep, dec, ms = C.c_int64(0), C.c_int64(0), (C.c_double * 7)()
+        check(lib().bc_bam_decoder_stats(self.h, C.byref(rep), C.byref(dec), C.byref(ms)))
+        return {"repaired": rep.value, "declined": dec.value, "upload_ms": ms[0], "inflate_ms": ms[1],
+                "index_ms": ms[2], "fill_ms": ms[3], "download_ms": ms[4], "fill_wall_ms": ms[5],
+                "next_wall_ms": ms[6]}
+
+    def drop(self) -> None:
+        """Let the pending bytes go (the stream is closed)."""
+        if self.h and self.ctx.h:
+            check(lib().bc_bam_decoder_drop(self.h))
+
+    def close(self) -> None:
+        if self.h and self.ctx.h:
+            lib().bc_bam_decoder_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def bam_batch_arrays(handle: int) -> BcBamArrays:
+    """The device pointers of a batch a BamDecoder produced (bcio_device_handle's handle)."""
+    a = BcBamArrays()
+    check(lib().bc_bam_batch_arrays(handle, C.byref(a)))
+    return a
+
+
+def bam_index_bytes(raw_bytes: int, seg_bytes: int = 0) -> int:
+    """bc_bam_index_bytes: the work buffer of bc_bam_index (seg_bytes 0: the default, 64 KiB)."""
+    n = C.c_size_t(0)
+    check(lib().bc_bam_index_bytes(int(raw_bytes), int(seg_bytes), C.byref(n)))
+    return int(n.value)
+
+
+class DeviceBamBatch:
+    """The arrays of one device-decoded batch (bcio_records' fields) in HBM; ``download()`` gives
+    them as numpy arrays, trimmed to the batch's sizes."""
+
+    def __init__(self, ctx: "Context", batch: BcBamBatch, want_qual: bool = True):
+        self.ctx, self.batch, self.want_qual = ctx, batch, bool(want_qual)
+        n, cw, sb = int(batch.n), int(batch.cigar_words), int(batch.seq_bytes)
+        self.sizes = {name: int(cnt(n, cw, sb)) for name, _, cnt in BAM_ARRAYS}
+        self.buffers = {}
+        self.arrays = BcBamArrays()
+        for name, dt, _ in BAM_ARRAYS:
+            if name == "qual" and not want_qual:
+                continue
+            buf = ctx.alloc(max(16, self.sizes[name] * np.dtype(dt).itemsize))
+            self.buffers[name] = buf
+            setattr(self.arrays, name, buf.ptr)
+        self.arrays.n_cap, self.arrays.cigar_cap, self.arrays.seq_cap = n, cw, sb
+
+    def download(self) -> dict:
+        out = {name: self.buffers[name].download(dt, self.sizes[name])
+               for name, dt, _ in BAM_ARRAYS if name in self.buffers}
+        out["n"] = int(self.batch.n)
+        return out
+
+    def free(self) -> None:
+        for b in self.buffers.values():
+            b.free()
+        self.buffers = {}
 
 
 def seq_event_bytes(seq_bytes: int) -> int:

@@ -79,20 +79,53 @@ def device_inflate_on() -> bool:
     return os.environ.get("BASECOUNT_DEVICE_INFLATE") not in (None, "", "0")
 
 
+# BASECOUNT_DEVICE_DECODE=1: the streams' records are decoded on the device too (DESIGN.md §3,
+# "Device record decode"): the inflated bytes stay in HBM, the batches' cigar / seq / qual arrays are
+# written where the kernels read them and only the per-record arrays come back.  Implies device
+# inflate; range streams (the sharded decode) keep the host decoder behind the device inflater.
+def device_decode_on() -> bool:
+    return os.environ.get("BASECOUNT_DEVICE_DECODE") not in (None, "", "0")
+
+
+_DECODE_MS = {"fills": 0, "upload_ms": 0.0, "inflate_ms": 0.0, "index_ms": 0.0, "fill_ms": 0.0, "download_ms": 0.0,
+              "fill_wall_ms": 0.0, "next_wall_ms": 0.0}
+
+
 def _open_stream(bam, device, **kw) -> BamStream:
-    if not device_inflate_on():
+    if not (device_inflate_on() or device_decode_on()):
         return BamStream(bam, **kw)
     dev = default_device() if device is None else int(device)
     ctx = _INFLATE_CONTEXTS.get(dev)
     if ctx is None:
         ctx = _INFLATE_CONTEXTS[dev] = D.Context(dev)
+    if device_decode_on() and "voff_range" not in kw:
+        # the qualities always come along: the fault paths read them on the host, and on the
+        # device they cost a store, no transfer
+        return BamStream(bam, device_decode=ctx, want_qual=True, **kw)
     return BamStream(bam, device_inflate=ctx, **kw)
+
+
+def _note_decode(stream) -> None:
+    """Add a stream's fills to PLAN["decode"] (before it is closed): decoded on the device, on the
+    host (declined fills), and the wrongly speculated segments the device hopped again."""
+    if getattr(stream, "decoder", None) is None or not getattr(stream, "_h", None):
+        return
+    st = stream.decode_stats()
+    rec = PLAN.setdefault("decode", {"device": 0, "host": 0, "repaired": 0})
+    for k in rec:
+        rec[k] += st[k]
+    t = stream.decoder.stats()
+    _DECODE_MS["fills"] += st["device"]
+    for k in _DECODE_MS:
+        if k != "fills":
+            _DECODE_MS[k] += t[k]
 
 
 def _note_inflate(stream) -> None:
     """Add a stream's inflated-block counts to PLAN["inflate"] (before it is closed): the blocks of
     its record fills; the few its open inflated on the host for the header are not counted, so
     with the option on "host" is the number of blocks the device refused."""
+    _note_decode(stream)
     st = stream.inflate_stats()
     if not st["callback"] and not st["host"]:
         return  # closed already
@@ -480,6 +513,13 @@ def _type_args(bam, batch_records_, mmq, wanted, ref_index):
 
 
 # ------------------------------------------------------------------------- device pipeline
+class _Resident:
+    """A device array somebody else owns (a device-decoded batch's): just its pointer."""
+
+    def __init__(self, ptr: int):
+        self.ptr = int(ptr)
+
+
 class _BatchOnDevice:
     """One decoded batch in HBM: CIGAR words, packed SEQ (BC_SEQ_EVENT), nibble-indexed QUAL and
     the per-read arrays of its selected reads (sliced per reference).  The buffers come from the
@@ -497,13 +537,21 @@ class _BatchOnDevice:
         self.sel = sel
         # reference spans per read (for the LDS window bound), from the decoder
         self.span = np.where(faulty, 0, sel.span)
-        self.d_cigar = scratch.get("b_cigar", max(4, f.cigar.nbytes)).upload(f.cigar)
-        # packed SEQ in the kernels' layout (BC_SEQ_EVENT, padded): the decoder built it while
-        # filling the records, so the upload is a plain copy (no device conversion pass)
-        assert f.seq_event.size == D.seq_event_bytes(f.seq.nbytes)
-        self.d_seq = scratch.get("b_seq", f.seq_event.size).upload(f.seq_event)
-        self.d_qual = scratch.get("b_qual", max(4, f.qual.nbytes)).upload(f.qual) if need_qual else None
-        self.n_cig, self.n_seq, self.n_qual = f.cigar.size, f.seq.size, f.qual.size
+        dev = getattr(f, "device_arrays", None)
+        if dev is not None:
+            # a device-decoded batch: the arrays are where bc_bam_fill wrote them (the batch owns
+            # them until it is closed; the loop synchronises before that); nothing is uploaded
+            self.d_cigar, self.d_seq = _Resident(dev["cigar"][0]), _Resident(dev["seq_event"][0])
+            self.d_qual = _Resident(dev["qual"][0]) if need_qual else None
+            self.n_cig, self.n_seq, self.n_qual = dev["cigar"][1], dev["seq"][1], 2 * dev["seq"][1]
+        else:
+            self.d_cigar = scratch.get("b_cigar", max(4, f.cigar.nbytes)).upload(f.cigar)
+            # packed SEQ in the kernels' layout (BC_SEQ_EVENT, padded): the decoder built it while
+            # filling the records, so the upload is a plain copy (no device conversion pass)
+            assert f.seq_event.size == D.seq_event_bytes(f.seq.nbytes)
+            self.d_seq = scratch.get("b_seq", f.seq_event.size).upload(f.seq_event)
+            self.d_qual = scratch.get("b_qual", max(4, f.qual.nbytes)).upload(f.qual) if need_qual else None
+            self.n_cig, self.n_seq, self.n_qual = f.cigar.size, f.seq.size, f.qual.size
         m = sel.pos.size
         self.d_pos = scratch.get("b_pos", max(4, 4 * m)).upload(self.pos)
         self.d_cb = scratch.get("b_cb", max(4, 4 * m)).upload(sel.cig_beg)
@@ -735,6 +783,7 @@ def get_basecounts(bam, references=None, min_base_quality=0, min_mapping_quality
     is released when it returns, unless it runs inside the CLI (run(), one process per command)
     or ``_keep_scratch`` asks to keep it for the next call (release_device_memory() frees it)."""
     PLAN["inflate"] = {"device": 0, "host": 0}  # BGZF blocks inflated by k_inflate / on the host
+    PLAN["decode"] = {"device": 0, "host": 0, "repaired": 0}  # fills decoded on the device / declined to the host
     try:
         return _get_basecounts_top(bam, references, min_base_quality, min_mapping_quality, chunk_size,
                                    show_n_bases, long_format, device, _mode, _tiles, _group)
@@ -1514,6 +1563,12 @@ def _timing_report(wall_s: float) -> None:
             continue
         print(f"basecount[{rank}] device inflate: {t['blocks']} blocks, upload {t['upload_ms']:.2f} ms, "
               f"kernel {t['kernel_ms']:.2f} ms, download {t['download_ms']:.2f} ms", file=sys.stderr)
+    if _DECODE_MS["fills"]:  # BASECOUNT_DEVICE_DECODE=1: inside the decode phase too
+        t = _DECODE_MS
+        print(f"basecount[{rank}] device decode: {t['fills']} fills, upload {t['upload_ms']:.2f} ms, "
+              f"k_inflate {t['inflate_ms']:.2f} ms, k_bam_speculate + k_bam_stitch {t['index_ms']:.2f} ms, "
+              f"k_bam_fill {t['fill_ms']:.2f} ms, download {t['download_ms']:.2f} ms; host wall in the fill calls "
+              f"{t['fill_wall_ms']:.2f} ms, in the batch calls {t['next_wall_ms']:.2f} ms", file=sys.stderr)
     print(f"basecount[{rank}] wall {wall_s * 1e3:.2f} ms", file=sys.stderr)
 
 

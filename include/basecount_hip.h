@@ -471,6 +471,120 @@ int bc_bgzf_inflate_host(void* ctx, const uint8_t* h_comp, uint64_t comp_bytes, 
  * output may be NULL.                                                                           */
 int bc_bgzf_inflate_host_times(bc_ctx* ctx, double* ms /* [3] */, int64_t* blocks);
 
+/* ---- BAM record decode on the device (DESIGN.md §3 "Device record decode") --------------------
+ * d_raw[0, raw_bytes) holds inflated BAM bytes (bc_bgzf_inflate's output); `first` is the offset of
+ * a record start in it.  bc_bam_index finds the record chain (segments of seg_bytes speculated in
+ * parallel, then verified from `first` by the record rules alone), bc_bam_fill writes the arrays of
+ * bcio.h's bcio_records, byte for byte what the host decoder produces from the same bytes.
+ * A fill the device cannot take is DECLINED, not failed: the call returns BC_OK, status says why and
+ * err_off where; the caller decodes that fill on the host, so every error is the host's own.    */
+#define BC_BAM_OK 0
+#define BC_BAM_PARTIAL_LEN 1 /* final, fewer than 4 bytes left at err_off                           */
+#define BC_BAM_PARTIAL 2     /* final, the record at err_off ends past the buffer                   */
+#define BC_BAM_SHORT 3       /* block_size < 32                                                     */
+#define BC_BAM_NEG_LSEQ 4    /* l_seq < 0                                                           */
+#define BC_BAM_FIELDS 5      /* the record is shorter than its fields                               */
+#define BC_BAM_TOO_LARGE 6   /* raw_bytes >= 2^31: offsets are 32-bit on the device                 */
+#define BC_BAM_REPAIRS 7     /* more wrongly speculated segments than 16 + segments / 4             */
+#define BC_BAM_INTERNAL 8
+#define BC_BAM_SEG_DEFAULT 65536u
+
+typedef struct bc_bam_batch {
+    int64_t n;            /* records taken: at most max_records, complete ones only                */
+    uint64_t used;        /* offset after the last record taken (the next fill's first byte)       */
+    uint64_t cigar_words; /* sizes of the arrays bc_bam_fill writes                                */
+    uint64_t seq_bytes;
+    int32_t status;       /* BC_BAM_*; non-zero: declined, n and the sizes are not to be used      */
+    int32_t reserved;
+    uint64_t err_off;
+    int64_t segments;     /* segments of the fill                                                  */
+    int64_t repaired;     /* segments whose speculated entry was wrong and that were hopped again  */
+    uint64_t raw_bytes;   /* the arguments the work buffer was laid out for (bc_bam_fill reads them) */
+    uint64_t seg_bytes;
+} bc_bam_batch;
+
+/* Device pointers of the output arrays (bcio_records' fields).  seq may be NULL (the kernels read
+ * seq_event only); qual is written only with want_qual and may be NULL without.                 */
+typedef struct bc_bam_arrays {
+    int32_t* tid;        /* [n] */
+    int32_t* pos;
+    uint16_t* flag;
+    uint8_t* mapq;
+    int32_t* l_seq;
+    int32_t* qstart;
+    int32_t* qend;
+    uint32_t* rec_err;
+    int64_t* ref_span;
+    uint64_t* cig_off;   /* [n + 1] */
+    uint64_t* seq_off;   /* [n + 1] */
+    uint32_t* cigar;     /* [cigar_words] */
+    uint8_t* seq;        /* [seq_bytes] BAM packing */
+    uint8_t* seq_event;  /* [bc_seq_event_bytes(seq_bytes)] BC_SEQ_EVENT, tail zeroed */
+    uint8_t* qual;       /* [2 * seq_bytes] by nibble index */
+    int64_t n_cap;       /* what the arrays hold; a batch that needs more is refused (BC_E_ARG) */
+    uint64_t cigar_cap;
+    uint64_t seq_cap;
+} bc_bam_arrays;
+
+/* Bytes of bc_bam_index's work buffer.  seg_bytes 0 = BC_BAM_SEG_DEFAULT, else 64 .. 2^24. */
+int bc_bam_index_bytes(uint64_t raw_bytes, uint32_t seg_bytes, size_t* bytes);
+/* Blocking (it returns the counts that size the arrays).  first <= raw_bytes, max_records >= 0
+ * (bcio_stream_next's contract: at most that many), final != 0: no bytes follow, so an incomplete
+ * last record declines the fill; n_refs bounds the reference ids the speculation believes.
+ * d_work: 16-byte aligned, work_bytes >= bc_bam_index_bytes.  BC_E_ARG before any device is touched:
+ * NULL pointer, first > raw_bytes, negative max_records / n_refs, seg_bytes out of range, small or
+ * misaligned work buffer.                                                                        */
+int bc_bam_index(bc_ctx* ctx, const uint8_t* d_raw, uint64_t raw_bytes, uint64_t first, int64_t max_records, int final,
+                 int32_t n_refs, uint32_t seg_bytes, void* d_work, size_t work_bytes, bc_bam_batch* h_out);
+/* Stream-ordered, no allocation, capturable: fills the arrays for the batch bc_bam_index left in
+ * d_work (h_batch: its result; status must be BC_BAM_OK).                                        */
+int bc_bam_fill(bc_ctx* ctx, const uint8_t* d_raw, const void* d_work, const bc_bam_batch* h_batch,
+                const bc_bam_arrays* d_out, int want_qual);
+
+/* A stream's record decoder (bcio.h: bcio_stream_set_decoder) on the device: the fills' compressed
+ * bytes are uploaded, inflated by k_inflate and decoded by the two calls above; the inflated bytes
+ * never leave HBM, the bytes behind a batch are carried device to device, and only the per-record
+ * arrays come back to the host.  The four callbacks have the types of bcio.h's bcio_decoder
+ * (user = the bc_bam_decoder*; bc_bam_host_batch has bcio_dev_batch's layout), so the stream calls
+ * them with no Python in between.  A fill with a block k_inflate refuses, a fill of 2 GiB or more
+ * and every fill bc_bam_index declines are declined: the host decodes them.
+ * A batch's handle owns one device allocation with its arrays (bc_bam_batch_arrays: the pointers;
+ * seq and, without want_qual, qual included or NULL as bc_bam_fill takes them); release frees it.
+ * Calls on one decoder are serial and blocking (each ends with its download).                   */
+typedef struct bc_bam_decoder bc_bam_decoder;
+typedef struct bc_bam_host_batch {
+    int64_t n;
+    uint64_t used;
+    uint64_t cigar_words, seq_bytes;
+    const int32_t* tid;
+    const int32_t* pos;
+    const uint16_t* flag;
+    const uint8_t* mapq;
+    const int32_t* l_seq;
+    const int32_t* qstart;
+    const int32_t* qend;
+    const uint32_t* rec_err;
+    const int64_t* ref_span;
+    const uint64_t* cig_off;
+    const uint64_t* seq_off;
+    void* handle;
+} bc_bam_host_batch;
+int bc_bam_decoder_create(bc_ctx* ctx, int want_qual, uint32_t seg_bytes, bc_bam_decoder** out);
+int bc_bam_decoder_destroy(bc_bam_decoder* d);
+int bc_bam_decoder_fill(void* user, int append, const uint8_t* h_carry, uint64_t carry_bytes, const uint8_t* h_comp,
+                        uint64_t comp_bytes, const bc_zblock* h_blocks, int64_t n, uint64_t inflated_bytes);
+int bc_bam_decoder_next(void* user, int64_t max_records, int final, int32_t n_refs, bc_bam_host_batch* out);
+int bc_bam_decoder_pending(void* user, uint8_t* h_dst, uint64_t* bytes);
+void bc_bam_decoder_release(void* user, void* handle);
+int bc_bam_batch_arrays(const void* handle, bc_bam_arrays* out);
+/* Cumulative: segments repaired, fills / batches declined, device time (hipEvent pairs) of
+ * ms[0] uploads, ms[1] k_inflate, ms[2] index kernels, ms[3] fill kernel, ms[4] downloads, and the
+ * host's wall time inside ms[5] the fill calls and ms[6] the next calls (allocations and
+ * synchronisation included).  Any output may be NULL.                                            */
+int bc_bam_decoder_stats(bc_bam_decoder* d, int64_t* repaired, int64_t* declined, double* ms /* [7] */);
+/* The pending bytes are let go (a stream that is closed before its end leaves some). */
+int bc_bam_decoder_drop(bc_bam_decoder* d);
+
 /* ---- Multi-GPU: one process per GPU, RCCL over xGMI ---------------------------
  * Counting needs no exchange: references are independent, so each rank owns whole references
  * and runs the single-GPU path on them.  What crosses GPUs is small: the per-reference results

@@ -151,6 +151,58 @@ int bcio_stream_inflate_stats(const bcio_stream* s, int64_t* blocks_by_callback,
 int bcio_inflate_blocks(const uint8_t* comp, uint64_t comp_bytes, const bcio_zblock* blocks, int64_t n, uint8_t* out,
                         uint64_t out_bytes, int nthreads);
 
+/* ---- a stream's record decoder -----------------------------------------------------------------
+ * A stream inflates each fill and decodes its records on the host.  A decoder, when set, is handed
+ * the fills instead: the block descriptors of a fill (as for an inflater) and, when the bytes not
+ * handed out yet are the host's, those carry bytes in front of them; it keeps the inflated bytes to
+ * itself (in device memory) and returns each batch as the per-record arrays of bcio_records in
+ * host memory plus an opaque handle that owns the batch's cigar / seq / seq_event / qual arrays.
+ * Whatever it declines is decoded on the host as without it, so every error of every file is the
+ * host decoder's own:
+ *   fill     0: the decoder now holds the blocks' bytes behind its own pending bytes (append != 0)
+ *            or behind carry[0, carry_bytes), which replace whatever it held (append == 0; the
+ *            first fill of a stream comes so); non-zero: declined, its state unchanged.  The stream then takes the pending bytes back
+ *            (`pending`) and inflates and decodes this fill itself.
+ *   next     the next at most max_records records of the pending bytes; final != 0: no byte follows.
+ *            0: *out is the batch (n == 0: nothing is left); 1: fewer than max_records complete
+ *            records are pending and more bytes may follow: nothing was consumed; 2: declined.
+ *   pending  dst == NULL: *bytes = the pending bytes' count; else they are copied to dst and dropped.
+ *   release  called once per handle, from bcio_close.
+ * The arrays of *out stay valid until the decoder's next call; the stream copies them.  Range
+ * streams (bcio_stream_open_range) and bcio_open keep the host decoder.  This library has no device
+ * dependency: basecount_hip.h's bc_bam_decoder_* functions have these types.
+ * bcio_stream_decode_stats: fills decoded by the decoder / on the host while a decoder was set.
+ * bcio_device_handle: the handle of a batch the decoder produced, NULL for a host batch; such a
+ * batch's bcio_records has cigar, seq, seq_event and qual NULL (sizes as usual).                 */
+typedef struct bcio_dev_batch {
+    int64_t n;
+    uint64_t used; /* pending bytes the batch consumed */
+    uint64_t cigar_words, seq_bytes;
+    const int32_t* tid;
+    const int32_t* pos;
+    const uint16_t* flag;
+    const uint8_t* mapq;
+    const int32_t* l_seq;
+    const int32_t* qstart;
+    const int32_t* qend;
+    const uint32_t* rec_err;
+    const int64_t* ref_span;
+    const uint64_t* cig_off; /* [n + 1] */
+    const uint64_t* seq_off; /* [n + 1] */
+    void* handle;
+} bcio_dev_batch;
+typedef struct bcio_decoder {
+    void* user;
+    int (*fill)(void* user, int append, const uint8_t* carry, uint64_t carry_bytes, const uint8_t* comp,
+                uint64_t comp_bytes, const bcio_zblock* blocks, int64_t n, uint64_t inflated_bytes);
+    int (*next)(void* user, int64_t max_records, int final, int32_t n_refs, bcio_dev_batch* out);
+    int (*pending)(void* user, uint8_t* dst, uint64_t* bytes);
+    void (*release)(void* user, void* handle);
+} bcio_decoder;
+int bcio_stream_set_decoder(bcio_stream* s, const bcio_decoder* d); /* NULL: host only */
+int bcio_stream_decode_stats(const bcio_stream* s, int64_t* fills_by_decoder, int64_t* fills_by_host);
+void* bcio_device_handle(const bcio_file* f);
+
 /* ---- one file decoded by several ranks (each only its own references' records) ----------------
  * Positions are BAM virtual offsets: (BGZF block file offset << 16) | offset in its inflated bytes.
  * bcio_find_ref_start: the position of the first record whose refID is >= tid or -1 (unmapped),
