@@ -104,6 +104,7 @@ class BamFile:
 
             a = D.bam_batch_arrays(dev)
             self._device_ctx = _device_ctx
+            self.device_records = a  # bc_bam_arrays: every array of the batch in HBM (bc_bam_select reads them)
             self.device_arrays = {
                 "cigar": (a.cigar or 0, int(self.cig_off[-1]) if n else 0), "seq": (a.seq or 0, int(r.seq_bytes)),
                 "seq_event": (a.seq_event or 0, int(r.seq_event_bytes)),

@@ -769,6 +769,37 @@ int bc_bam_decoder_stats(bc_bam_decoder* d, int64_t* repaired, int64_t* declined
     return BC_OK;
 }
 
+// ---- read selection on the device (bc_select.hip) ----
+int bc_bam_select_bytes(int64_t n, int64_t n_refs, size_t* bytes) {
+    if (!bytes) return fail(BC_E_ARG, "bc_bam_select_bytes: bytes is NULL");
+    if (n < 0 || n_refs < 0) return fail(BC_E_ARG, "bc_bam_select_bytes: negative n or n_refs");
+    if (n > 0x7FFFFFFFll - 1) return fail(BC_E_ARG, "bc_bam_select_bytes: n must be below 2^31");
+    *bytes = bc::select_bytes(n, n_refs);
+    return BC_OK;
+}
+
+int bc_bam_select(bc_ctx* c, const bc_bam_arrays* r, int64_t n, int64_t min_mapq, const uint8_t* d_ref_sel,
+                  const int64_t* d_ref_len, int32_t n_refs, void* d_work, size_t work_bytes, const bc_sel_arrays* o) {
+    if (!c) return fail(BC_E_ARG, "ctx is NULL");
+    if (!r || !d_ref_sel || !d_ref_len || !d_work || !o) return fail(BC_E_ARG, "bc_bam_select: NULL pointer");
+    if (n < 0 || n_refs < 0) return fail(BC_E_ARG, "bc_bam_select: negative n or n_refs");
+    if (n > 0x7FFFFFFFll - 1) return fail(BC_E_ARG, "bc_bam_select: n must be below 2^31");
+    if (!r->tid || !r->pos || !r->flag || !r->mapq || !r->qstart || !r->qend || !r->rec_err || !r->ref_span ||
+        !r->cig_off || !r->seq_off)
+        return fail(BC_E_ARG, "bc_bam_select: NULL pointer among the record arrays");
+    if (!o->pos || !o->cig_beg || !o->cig_n || !o->seq_nib || !o->qlen || !o->span || !o->rec || !o->ordinal ||
+        !o->ref_beg || !o->max_span || !o->max_end || !o->n_reads || !o->n_complex || !o->sum_ops || !o->err_or ||
+        !o->flags || !o->header)
+        return fail(BC_E_ARG, "bc_bam_select: NULL pointer among the output arrays");
+    if (r->n_cap < n) return fail(BC_E_ARG, "bc_bam_select: the record arrays hold fewer than n records");
+    if (o->n_cap < n || o->ref_cap < n_refs) return fail(BC_E_ARG, "bc_bam_select: the output arrays are smaller than n / n_refs");
+    if (work_bytes < bc::select_bytes(n, n_refs)) return fail(BC_E_ARG, "bc_bam_select: d_work smaller than bc_bam_select_bytes");
+    if ((uintptr_t)d_work & 15u) return fail(BC_E_ARG, "bc_bam_select: d_work must be 16-byte aligned");
+    DeviceGuard g(c->device);
+    HIP_TRY(bc::launch_select(c->stream, *r, n, min_mapq, d_ref_sel, d_ref_len, n_refs, d_work, *o));
+    return BC_OK;
+}
+
 int bc_ctx_stream(bc_ctx* c, void** s) {
     if (!c || !s) return fail(BC_E_ARG, "NULL argument");
     *s = (void*)c->stream;

@@ -209,4 +209,9 @@ hipError_t launch_bam_index(hipStream_t s, const uint8_t* raw, uint32_t N, uint3
 hipError_t launch_bam_fill(hipStream_t s, const uint8_t* raw, uint32_t N, uint32_t seg_bytes, const void* work,
                            const bc_bam_arrays& out, bool want_qual);
 
+// ---- read selection (bc_select.hip over bc_select.h): 0 <= n < 2^31 is the caller's check ----
+size_t select_bytes(int64_t n, int64_t n_refs);
+hipError_t launch_select(hipStream_t s, const bc_bam_arrays& rec, int64_t n, int64_t min_mapq, const uint8_t* ref_sel,
+                         const int64_t* ref_len, int32_t n_refs, void* work, const bc_sel_arrays& out);
+
 }  // namespace bc

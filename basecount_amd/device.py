@@ -78,6 +78,59 @@ class BcBamArrays(C.Structure):
         ("n_cap", C.c_int64), ("cigar_cap", C.c_uint64), ("seq_cap", C.c_uint64)]
 
 
+class BcSelHeader(C.Structure):
+    """bc_sel_header: what bc_bam_select found (status != 0: declined, select on the host)."""
+    _fields_ = [("status", C.c_int32), ("err_or", C.c_uint32), ("n_accepted", C.c_int64), ("n_selected", C.c_int64),
+                ("keyerror_rec", C.c_int64), ("keyerror_ordinal", C.c_int64), ("reserved", C.c_int64 * 3)]
+
+
+SEL_HEADER_DTYPE = np.dtype([("status", "<i4"), ("err_or", "<u4"), ("n_accepted", "<i8"), ("n_selected", "<i8"),
+                             ("keyerror_rec", "<i8"), ("keyerror_ordinal", "<i8"), ("reserved", "<i8", (3,))])  # 64 bytes
+# bc_sel_arrays' device arrays, in the struct's order: per selected read, then per reference
+SEL_READ_ARRAYS = (("pos", np.int32), ("cig_beg", np.uint32), ("cig_n", np.uint32), ("seq_nib", np.uint32),
+                   ("qlen", np.uint32), ("span", np.int64), ("rec", np.int64), ("ordinal", np.int64))
+SEL_REF_ARRAYS = (("ref_beg", np.int64), ("max_span", np.int64), ("max_end", np.int64), ("n_reads", np.int64),
+                  ("n_complex", np.int64), ("sum_ops", np.uint64), ("err_or", np.uint32), ("flags", np.uint32))
+SEL_STATUS = ("ok", "ungrouped", "too_large")  # BC_SEL_*
+SEL_SORTED, SEL_INSIDE = 1, 2
+
+
+class BcSelArrays(C.Structure):
+    _fields_ = ([(name, C.c_void_p) for name, _ in SEL_READ_ARRAYS] + [("n_cap", C.c_int64)]
+                + [(name, C.c_void_p) for name, _ in SEL_REF_ARRAYS] + [("ref_cap", C.c_int64), ("header", C.c_void_p)])
+
+
+def sel_layout(n_cap: int, ref_cap: int) -> tuple:
+    """One buffer for bc_bam_select's outputs: ({name: byte offset}, bytes of the leading part the
+    host downloads (the header and the per-reference arrays), total bytes)."""
+    off, at = {"header": 0}, 256
+    for name, dt in SEL_REF_ARRAYS:
+        off[name] = at
+        at += (np.dtype(dt).itemsize * (ref_cap + 1) + 255) // 256 * 256
+    small = at
+    for name, dt in SEL_READ_ARRAYS:
+        off[name] = at
+        at += (np.dtype(dt).itemsize * max(1, n_cap) + 255) // 256 * 256
+    return off, small, at
+
+
+def sel_arrays(base: int, n_cap: int, ref_cap: int) -> BcSelArrays:
+    """bc_sel_arrays pointing into a buffer of sel_layout(n_cap, ref_cap) at device address base."""
+    off, _, _ = sel_layout(n_cap, ref_cap)
+    a = BcSelArrays()
+    for name, o in off.items():
+        setattr(a, name, base + o)
+    a.n_cap, a.ref_cap = int(n_cap), int(ref_cap)
+    return a
+
+
+def bam_select_bytes(n: int, n_refs: int) -> int:
+    """bc_bam_select_bytes: the work buffer of bc_bam_select."""
+    b = C.c_size_t(0)
+    check(lib().bc_bam_select_bytes(int(n), int(n_refs), C.byref(b)))
+    return int(b.value)
+
+
 BAM_STATUS = ("ok", "partial_len", "partial", "short", "neg_lseq", "fields", "too_large", "repairs", "internal")  # BC_BAM_*
 
 
@@ -181,6 +234,10 @@ def lib() -> C.CDLL:
         "bc_bam_batch_arrays": ([vp, C.POINTER(BcBamArrays)], C.c_int),
         "bc_bam_decoder_stats": ([vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(dbl * 7)], C.c_int),
         "bc_bam_decoder_drop": ([vp], C.c_int),
+        # read selection on the device (bc_select.hip)
+        "bc_bam_select_bytes": ([i64, i64, C.POINTER(C.c_size_t)], C.c_int),
+        "bc_bam_select": ([vp, C.POINTER(BcBamArrays), i64, i64, vp, vp, C.c_int32, vp, C.c_size_t,
+                           C.POINTER(BcSelArrays)], C.c_int),
         # multi-GPU (bc_comm.hip)
         "bc_comm_unique_id": ([vp], C.c_int),
         "bc_comm_init": ([vp, vp, C.c_int, C.c_int, C.POINTER(vp)], C.c_int),
@@ -514,6 +571,14 @@ class Context:
         self.sync()  # the work buffer is released here; the arrays are complete
         work.free()
         return b, out
+
+    def bam_select(self, rec: BcBamArrays, n: int, min_mapq: int, d_ref_sel: int, d_ref_len: int, n_refs: int,
+                   d_work: int, work_bytes: int, out: BcSelArrays) -> None:
+        """bc_bam_select: bcio_select on a decoded batch's device arrays, stream-ordered (capturable,
+        no allocation).  The header's status says whether the outputs are to be used."""
+        mmq = max(min(int(min_mapq), 1 << 40), -(1 << 40))
+        check(lib().bc_bam_select(self.h, C.byref(rec), int(n), mmq, d_ref_sel, d_ref_len, int(n_refs), d_work,
+                                  int(work_bytes), C.byref(out)))
 
     def capture(self, fn) -> "Graph":
         """Record the compute calls made by fn() into a hipGraph (replay with Graph.launch)."""

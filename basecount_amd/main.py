@@ -84,7 +84,15 @@ def device_inflate_on() -> bool:
 # written where the kernels read them and only the per-record arrays come back.  Implies device
 # inflate; range streams (the sharded decode) keep the host decoder behind the device inflater.
 def device_decode_on() -> bool:
-    return os.environ.get("BASECOUNT_DEVICE_DECODE") not in (None, "", "0")
+    return os.environ.get("BASECOUNT_DEVICE_DECODE") not in (None, "", "0") or device_select_on()
+
+
+# BASECOUNT_DEVICE_SELECT=1: a device-decoded batch's reads are selected on the device as well
+# ("Device read selection"): bc_bam_select filters and splits the records where
+# bc_bam_fill left them, the pileup kernels read the selection's pos / cig_beg / cig_n / seq_nib in
+# place, and the host sees the header and one row per reference.  Implies device decode.
+def device_select_on() -> bool:
+    return os.environ.get("BASECOUNT_DEVICE_SELECT") not in (None, "", "0")
 
 
 _DECODE_MS = {"fills": 0, "upload_ms": 0.0, "inflate_ms": 0.0, "index_ms": 0.0, "fill_ms": 0.0, "download_ms": 0.0,
@@ -520,6 +528,100 @@ class _Resident:
         self.ptr = int(ptr)
 
 
+class _DeviceElems:
+    """Single elements of a device array, read where they lie (8 bytes a read)."""
+
+    def __init__(self, ctx, ptr: int, dtype):
+        self.ctx, self.ptr, self.dtype = ctx, int(ptr), np.dtype(dtype)
+
+    def __getitem__(self, i):
+        out = np.empty(1, self.dtype)
+        D.check(D.lib().bc_memcpy_d2h(self.ctx.h, out.ctypes.data, self.ptr + int(i) * self.dtype.itemsize,
+                                      self.dtype.itemsize))
+        self.ctx.sync()
+        return out[0]
+
+
+class DeviceSelection:
+    """bc_bam_select's result standing in for bam.Selection: the header, ``ref_beg`` and one row per
+    reference on the host (``facts``: max_span, max_end, n_reads, n_complex, sum_ops, err_or,
+    flags), the per-read arrays in HBM (``d``: name -> device pointer; ``ordinal`` / ``rec`` read
+    single elements from there)."""
+
+    def __init__(self, ctx, hdr, ref_beg, facts, ptrs):
+        self.status = int(hdr["status"])
+        self.err_or = int(hdr["err_or"])
+        self.n_accepted = int(hdr["n_accepted"])
+        self.n_selected = int(hdr["n_selected"])
+        self.keyerror_rec = int(hdr["keyerror_rec"])
+        self.keyerror_ordinal = int(hdr["keyerror_ordinal"])
+        self.ref_beg, self.facts, self.d = ref_beg, facts, ptrs
+        self.ordinal = _DeviceElems(ctx, ptrs["ordinal"], np.int64)
+        self.rec = _DeviceElems(ctx, ptrs["rec"], np.int64)
+
+    def regular(self) -> bool:
+        """Nothing the host paths must see: selected on the device, no faulty read, no keyerror."""
+        return self.status == 0 and self.err_or == 0 and self.keyerror_ordinal < 0
+
+
+_SELECT_MS = {"calls": 0, "device_ms": 0.0}
+SELECT_TIMING = False  # event pairs around bc_bam_select without BASECOUNT_HIP_TIMING (scripts/select_bench.py)
+
+
+class _DeviceSelector:
+    """bc_bam_select for the device-decoded batches of one stream, on the decoder's context: the
+    requested references and the lengths uploaded once, a work buffer and two output slots (the
+    current batch's selection is read by its kernels while the next batch's is made), grown on
+    demand and freed with the call."""
+
+    def __init__(self, ctx, wanted, lengths):
+        self.ctx, self.n_refs = ctx, len(wanted)
+        self.d_sel = ctx.alloc(max(16, self.n_refs)).upload(np.asarray(wanted, np.uint8))
+        self.d_len = ctx.alloc(max(16, 8 * self.n_refs)).upload(np.asarray(lengths, np.int64))
+        self.work = None
+        self.slots = [None, None]
+        self.turn = 0
+        self.timing = bool(os.environ.get("BASECOUNT_HIP_TIMING")) or SELECT_TIMING
+
+    def _grown(self, buf, nbytes):
+        if buf is None or buf.nbytes < nbytes:
+            if buf is not None:
+                self.ctx.sync()
+                buf.free()
+            buf = self.ctx.alloc(max(16, nbytes + nbytes // 4))
+        return buf
+
+    def select(self, f: BamFile, mmq) -> DeviceSelection:
+        n, nr, ctx = int(f.n_records), self.n_refs, self.ctx
+        off, small, total = D.sel_layout(n, nr)
+        self.work = self._grown(self.work, D.bam_select_bytes(n, nr))
+        self.turn ^= 1
+        out = self.slots[self.turn] = self._grown(self.slots[self.turn], total)
+        arrays = D.sel_arrays(out.ptr, n, nr)
+        if self.timing:
+            ctx.event_record(2)
+        ctx.bam_select(f.device_records, n, mmq, self.d_sel.ptr, self.d_len.ptr, nr, self.work.ptr, self.work.nbytes,
+                       arrays)
+        if self.timing:
+            ctx.event_record(3)
+        raw = out.download(np.uint8, small)  # (synchronises: the selection is complete)
+        if self.timing:
+            _SELECT_MS["calls"] += 1
+            _SELECT_MS["device_ms"] += ctx.event_elapsed_ms(2, 3)
+        hdr = raw[:64].view(D.SEL_HEADER_DTYPE)[0]
+        rows = {name: raw[off[name]:off[name] + np.dtype(dt).itemsize * (nr + (name == "ref_beg"))].view(dt)
+                for name, dt in D.SEL_REF_ARRAYS}
+        ref_beg = rows.pop("ref_beg")
+        return DeviceSelection(ctx, hdr, ref_beg, rows, {name: out.ptr + off[name] for name, _ in D.SEL_READ_ARRAYS})
+
+    def release(self):
+        self.ctx.sync()
+        for b in [self.d_sel, self.d_len, self.work] + self.slots:
+            if b is not None:
+                b.free()
+        self.work, self.slots = None, [None, None]
+
+
 class _BatchOnDevice:
     """One decoded batch in HBM: CIGAR words, packed SEQ (BC_SEQ_EVENT), nibble-indexed QUAL and
     the per-read arrays of its selected reads (sliced per reference).  The buffers come from the
@@ -528,6 +630,18 @@ class _BatchOnDevice:
 
     def __init__(self, ctx: D.Context, f: BamFile, sel, need_qual: bool, scratch):
         self.ctx = ctx
+        self.sel = sel
+        self.facts = getattr(sel, "facts", None)
+        if self.facts is not None:
+            # selected on the device (a regular batch: no faulty read to mask): the per-read arrays
+            # are where bc_bam_select wrote them, the batch's own where bc_bam_fill did; no upload
+            dev = f.device_arrays
+            self.d_cigar, self.d_seq = _Resident(dev["cigar"][0]), _Resident(dev["seq_event"][0])
+            self.d_qual = _Resident(dev["qual"][0]) if need_qual else None
+            self.n_cig, self.n_seq, self.n_qual = dev["cigar"][1], dev["seq"][1], 2 * dev["seq"][1]
+            self.d_pos, self.d_cb = _Resident(sel.d["pos"]), _Resident(sel.d["cig_beg"])
+            self.d_cn, self.d_sn = _Resident(sel.d["cig_n"]), _Resident(sel.d["seq_nib"])
+            return
         rec_err = f.rec_err[sel.rec] if sel.rec.size else np.zeros(0, np.uint32)
         faulty = (rec_err & (_TYPE_FAULTS | REC_BAD_CLIP)) != 0
         # faulty reads raise before their counts could matter: give them no CIGAR so the range
@@ -581,6 +695,16 @@ class _BatchOnDevice:
         if self.d_qual is not None:
             r.qual = self.d_qual.ptr
             r.qual_bytes = self.n_qual
+        if self.facts is not None:
+            # the references of [b0, b1): the facts' rows (a run's order flag does not matter: the
+            # segmented launch places its reads itself)
+            rb, fa = self.sel.ref_beg, self.facts
+            t0, t1 = int(np.searchsorted(rb, b0, "right")) - 1, int(np.searchsorted(rb, b1, "left"))
+            has = fa["n_reads"][t0:t1] > 0
+            r.sorted = int(bool(np.all(fa["flags"][t0:t1] & D.SEL_SORTED))) if b1 - b0 > 1 else 1
+            r.max_span = int(min(int(fa["max_span"][t0:t1].max()), 2**31 - 1)) if b1 > b0 else 0
+            r.max_end = int(fa["max_end"][t0:t1][has].max()) if b1 > b0 else 0
+            return r
         pos = self.pos[b0:b1]
         r.sorted = int(bool(np.all(pos[1:] >= pos[:-1]))) if b1 - b0 > 1 else 1
         r.max_span = int(min(self.span[b0:b1].max(), 2**31 - 1)) if b1 > b0 else 0
@@ -634,6 +758,24 @@ def wants_ops(cig_n) -> bool:
     if c.size == 0:
         return False
     return bool(np.mean(c > 8) >= OPS_MIN_SHARE and float(c.mean()) >= OPS_MIN_MEAN)
+
+
+def wants_ops_counts(n, n_complex, sum_ops) -> bool:
+    """wants_ops for a slice known by its counts: n reads, n_complex of them with more than 8 CIGAR
+    ops, sum_ops ops in all (a group: the sums over its references).  The same answer as
+    wants_ops(cig_n) for every input: the sums are exact integers below 2^53, so both divisions
+    give numpy's doubles."""
+    v = os.environ.get("BASECOUNT_LONG_READS", "")
+    if v == "0":
+        return False
+    if v == "1":
+        return True
+    if v == "" and not OPS_RULE_DEFAULT:
+        return False
+    n = int(n)
+    if n == 0:
+        return False
+    return bool(int(n_complex) / n >= OPS_MIN_SHARE and int(sum_ops) / n >= OPS_MIN_MEAN)
 
 
 @contextlib.contextmanager
@@ -784,6 +926,7 @@ def get_basecounts(bam, references=None, min_base_quality=0, min_mapping_quality
     or ``_keep_scratch`` asks to keep it for the next call (release_device_memory() frees it)."""
     PLAN["inflate"] = {"device": 0, "host": 0}  # BGZF blocks inflated by k_inflate / on the host
     PLAN["decode"] = {"device": 0, "host": 0, "repaired": 0}  # fills decoded on the device / declined to the host
+    PLAN.pop("select", None)  # BASECOUNT_DEVICE_SELECT: batches selected on the device / on the host (set by the run)
     try:
         return _get_basecounts_top(bam, references, min_base_quality, min_mapping_quality, chunk_size,
                                    show_n_bases, long_format, device, _mode, _tiles, _group)
@@ -821,6 +964,7 @@ def _get_basecounts_top(bam, references, min_base_quality, min_mapping_quality, 
 def _get_basecounts(bam, references, min_base_quality, min_mapping_quality, chunk_size, show_n_bases,
                     long_format, device, _mode, _tiles, _group, grouped, sharded=False):
     stream = _open_stream(bam, device)
+    selector = None  # BASECOUNT_DEVICE_SELECT: the device-decoded batches of an unsharded run
     try:
         references = get_references(stream, references)
         names = stream.references
@@ -905,8 +1049,40 @@ def _get_basecounts(bam, references, min_base_quality, min_mapping_quality, chun
         def tiles_of(ref):
             return _tiles(ref) if _tiles else None
 
-        def run_group(tids, reads, read_beg, cig_n=()):
-            ops = wants_ops(cig_n)
+        if device_select_on() and not sharded and getattr(stream, "decoder", None) is not None:
+            selector = _DeviceSelector(stream._decode_ctx, wanted, stream.lengths)
+            PLAN["select"] = {"device": 0, "host": 0, "declined": [], "redone": 0}
+
+        def select(b):
+            """The batch's selection: on the device when it was decoded there and nothing is
+            irregular (a decline, a faulty read, a keyerror), else bcio_select as ever."""
+            if selector is None:
+                return b.select(mmq, wanted)
+            if b.device_arrays is None:  # a fill the device decoder declined
+                PLAN["select"]["host"] += 1
+                return b.select(mmq, wanted)
+            s = selector.select(b, mmq)
+            if s.regular():
+                PLAN["select"]["device"] += 1
+                return s
+            if s.status != 0:
+                PLAN["select"]["declined"].append(D.SEL_STATUS[s.status])
+            else:
+                PLAN["select"]["redone"] += 1
+            return b.select(mmq, wanted)
+
+        def ops_of(bod, t_first, t_last):
+            """wants_ops for the reads of the references t_first .. t_last of the batch."""
+            if bod.facts is not None:
+                fa = bod.facts
+                return wants_ops_counts(int(fa["n_reads"][t_first:t_last + 1].sum()),
+                                        int(fa["n_complex"][t_first:t_last + 1].sum()),
+                                        int(fa["sum_ops"][t_first:t_last + 1].sum()))
+            return wants_ops(bod.cig_n[int(bod.sel.ref_beg[t_first]):int(bod.sel.ref_beg[t_last + 1])])
+
+        def run_group(tids, reads, read_beg, ops=None):
+            if ops is None:  # a group without reads
+                ops = wants_ops(())
             with _ops_shape(ctx, ops):
                 res = _device_group(ctx, reads, [int(lens_t[t]) for t in tids], read_beg, mbq, k, nf, nf2, _mode,
                                     scratch)
@@ -932,7 +1108,11 @@ def _get_basecounts(bam, references, min_base_quality, min_mapping_quality, chun
                     and (nsel is None or int(nsel.ref_beg[t + 1]) == int(nsel.ref_beg[t])))
             if int(elig.sum()) < 2:
                 return []
-            elig &= _reads_inside(bod.pos, bod.span, sel.ref_beg, lens_t)[t_a:t_b + 1]
+            if bod.facts is not None:  # the same two properties, from the device's rows
+                both = D.SEL_SORTED | D.SEL_INSIDE
+                elig &= (bod.facts["flags"][t_a:t_b + 1] & both) == both
+            else:
+                elig &= _reads_inside(bod.pos, bod.span, sel.ref_beg, lens_t)[t_a:t_b + 1]
             return plan_groups(lens_t[t_a:t_b + 1], elig, cap, first=t_a)
 
         base = 0  # accepted reads before the current batch (global ordinals; sharded: in the range)
@@ -961,17 +1141,19 @@ def _get_basecounts(bam, references, min_base_quality, min_mapping_quality, chun
                     if bool(np.any(((tids < t_lo) | (tids >= t_hi)) & (tids != -1))):
                         raise _ShardMiss()
                 with _phase("select"):
-                    sel = sel_next if sel_next is not None else f.select(mmq, wanted)
+                    sel = sel_next if sel_next is not None else select(f)
                 sel_next = None
+                on_dev = isinstance(sel, DeviceSelection)  # a regular batch: no read of it is faulty
                 fl.n_records += f.n_records
                 # in-loop faults (global ordinals); type faults per reference
                 if fl.keyerror is None and sel.keyerror_ordinal >= 0:
                     t = int(f.tid[sel.keyerror_rec])
                     fl.keyerror = (base + sel.keyerror_ordinal, names[t] if 0 <= t < len(names) else None)
-                rec_err = f.rec_err[sel.rec] if sel.rec.size else np.zeros(0, np.uint32)
-                clip = (rec_err & REC_BAD_CLIP) != 0
-                if fl.clip is None and clip.any():
-                    fl.clip = base + int(sel.ordinal[np.argmax(clip)])
+                if not on_dev:
+                    rec_err = f.rec_err[sel.rec] if sel.rec.size else np.zeros(0, np.uint32)
+                    clip = (rec_err & REC_BAD_CLIP) != 0
+                    if fl.clip is None and clip.any():
+                        fl.clip = base + int(sel.ordinal[np.argmax(clip)])
                 here = []
                 for ref in ref_order:
                     t = ref_index[ref]
@@ -979,9 +1161,10 @@ def _get_basecounts(bam, references, min_base_quality, min_mapping_quality, chun
                     if b1 == b0:
                         continue
                     nreads[ref] += b1 - b0
-                    m = (rec_err[b0:b1] & _TYPE_FAULTS) != 0
-                    if fl.type_ord.get(ref, -1) < 0 and m.any():
-                        fl.type_ord[ref] = base + int(sel.ordinal[b0 + int(np.argmax(m))])
+                    if not on_dev:
+                        m = (rec_err[b0:b1] & _TYPE_FAULTS) != 0
+                        if fl.type_ord.get(ref, -1) < 0 and m.any():
+                            fl.type_ord[ref] = base + int(sel.ordinal[b0 + int(np.argmax(m))])
                     if t in mine_t:
                         here.append(ref)
                 # one batch of look-ahead: a reference absent from the next batch is complete
@@ -992,7 +1175,7 @@ def _get_basecounts(bam, references, min_base_quality, min_mapping_quality, chun
                     if any(r in finished for r in here):
                         raise _ShardMiss() if sharded else _Ungrouped()
                     with _phase("select"):
-                        nsel = sel_next = nxt.select(mmq, wanted) if (nxt is not None and grouped) else None
+                        nsel = sel_next = select(nxt) if (nxt is not None and grouped) else None
                     with _phase("upload"):
                         bod = _BatchOnDevice(ctx, f, sel, need_qual=mbq > 0, scratch=scratch)
                     t_refs = _phase("kernels + download")
@@ -1003,7 +1186,7 @@ def _get_basecounts(bam, references, min_base_quality, min_mapping_quality, chun
                             b0 = int(sel.ref_beg[tids[0]])
                             run_group(tids, bod.reads_run(tids[0], tids[-1]),
                                       [int(sel.ref_beg[t]) - b0 for t in tids] + [int(sel.ref_beg[tids[-1] + 1]) - b0],
-                                      bod.cig_n[b0:int(sel.ref_beg[tids[-1] + 1])])
+                                      ops_of(bod, tids[0], tids[-1]))
                             in_group.update(names[t] for t in tids)
                     for ref in here:
                         if ref in in_group:  # (cannot have a range fault: every read lies inside)
@@ -1015,7 +1198,7 @@ def _get_basecounts(bam, references, min_base_quality, min_mapping_quality, chun
                         closed = grouped and ref not in split and (
                             nxt is None or int(nsel.ref_beg[t + 1]) == int(nsel.ref_beg[t]))
                         b0 = int(sel.ref_beg[t])
-                        ops = wants_ops(bod.cig_n[b0:int(sel.ref_beg[t + 1])])
+                        ops = ops_of(bod, t, t)
                         if ops and ref not in PLAN["ops"]:
                             PLAN["ops"].append(ref)
                         if closed and ref not in acc:  # the whole reference in this batch: fused
@@ -1144,6 +1327,8 @@ def _get_basecounts(bam, references, min_base_quality, min_mapping_quality, chun
             return out, owner, ref_order
         return out
     finally:
+        if selector is not None:
+            selector.release()
         _note_inflate(stream)
         _release(stream)
 
@@ -1569,6 +1754,9 @@ def _timing_report(wall_s: float) -> None:
               f"k_inflate {t['inflate_ms']:.2f} ms, k_bam_speculate + k_bam_stitch {t['index_ms']:.2f} ms, "
               f"k_bam_fill {t['fill_ms']:.2f} ms, download {t['download_ms']:.2f} ms; host wall in the fill calls "
               f"{t['fill_wall_ms']:.2f} ms, in the batch calls {t['next_wall_ms']:.2f} ms", file=sys.stderr)
+    if _SELECT_MS["calls"]:  # BASECOUNT_DEVICE_SELECT=1: inside the select phase too
+        print(f"basecount[{rank}] device select: {_SELECT_MS['calls']} batches, k_sel_count .. k_sel_facts "
+              f"{_SELECT_MS['device_ms']:.3f} ms", file=sys.stderr)
     print(f"basecount[{rank}] wall {wall_s * 1e3:.2f} ms", file=sys.stderr)
 
 

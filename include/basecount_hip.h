@@ -585,6 +585,75 @@ int bc_bam_decoder_stats(bc_bam_decoder* d, int64_t* repaired, int64_t* declined
 /* The pending bytes are let go (a stream that is closed before its end leaves some). */
 int bc_bam_decoder_drop(bc_bam_decoder* d);
 
+/* ---- Read selection on the device (bc_select.hip over bc_select.h) -----------------------------
+ * bcio_select (bcio.h) on the record arrays bc_bam_fill left in HBM, bit for bit: a record is
+ * accepted when !(flag & 4) && mapq >= min_mapq, wanted when 0 <= tid < n_refs && d_ref_sel[tid],
+ * selected when both.  The selected reads come out by reference, file order within a reference:
+ *   pos, cig_beg = (uint32)cig_off[i], cig_n = (uint32)(cig_off[i+1] - cig_off[i]),
+ *   seq_nib = (uint32)(2 seq_off[i] + max(0, qstart[i])), qlen = (uint32)max(0, qend[i] - qstart[i]),
+ *   span = ref_span[i], rec = i, ordinal = accepted records before i (wanted or not);
+ * ref_beg[n_refs + 1] slices them.  Per reference, so that the host reads no per-read array:
+ *   max_span (0 without reads), max_end = max(pos + span) (0 without reads), n_reads,
+ *   n_complex = reads with cig_n > 8, sum_ops = sum of cig_n, err_or = OR of the reads' rec_err,
+ *   flags: BC_SEL_SORTED pos is non-decreasing within the reference, BC_SEL_INSIDE every read has
+ *   0 <= pos and pos + span <= d_ref_len[tid] (64-bit).
+ * The header: n_accepted, n_selected, the first accepted record that is not wanted and its ordinal
+ * (-1 / -1 without one), the OR of rec_err over the selected reads, and a status.
+ * Declined, never failed: the device handles the batches whose selected reads have non-decreasing
+ * tid (a coordinate-sorted or reference-grouped file; unselected records in between do not matter);
+ * any other has status BC_SEL_UNGROUPED, and a batch whose cig_off[n] or 2 * seq_off[n] is above
+ * 2^32 - 1 has BC_SEL_TOO_LARGE (it wins when both hold).  The call still returns BC_OK; with a
+ * non-zero status only the header's status is to be trusted: run bcio_select on the host.       */
+#define BC_SEL_OK 0
+#define BC_SEL_UNGROUPED 1
+#define BC_SEL_TOO_LARGE 2
+#define BC_SEL_SORTED 1u
+#define BC_SEL_INSIDE 2u
+
+typedef struct bc_sel_header {
+    int32_t status;   /* BC_SEL_* */
+    uint32_t err_or;
+    int64_t n_accepted;
+    int64_t n_selected;
+    int64_t keyerror_rec;
+    int64_t keyerror_ordinal;
+    int64_t reserved[3];
+} bc_sel_header;
+
+/* Device pointers of the outputs and what they hold: n_cap reads, ref_cap references
+ * (ref_beg: ref_cap + 1 entries).                                                             */
+typedef struct bc_sel_arrays {
+    int32_t* pos;
+    uint32_t* cig_beg;
+    uint32_t* cig_n;
+    uint32_t* seq_nib;
+    uint32_t* qlen;
+    int64_t* span;
+    int64_t* rec;
+    int64_t* ordinal;
+    int64_t n_cap;
+    int64_t* ref_beg;
+    int64_t* max_span;
+    int64_t* max_end;
+    int64_t* n_reads;
+    int64_t* n_complex;
+    uint64_t* sum_ops;
+    uint32_t* err_or;
+    uint32_t* flags;     /* BC_SEL_SORTED | BC_SEL_INSIDE */
+    int64_t ref_cap;
+    bc_sel_header* header;
+} bc_sel_arrays;
+
+/* Bytes of bc_bam_select's work buffer for n records (0 <= n < 2^31, n_refs >= 0). */
+int bc_bam_select_bytes(int64_t n, int64_t n_refs, size_t* bytes);
+/* Stream-ordered, no allocation, no synchronisation: capturable.  d_rec: the arrays of n records
+ * (tid, pos, flag, mapq, qstart, qend, rec_err, ref_span, cig_off[n + 1], seq_off[n + 1] are read);
+ * d_ref_sel: n_refs bytes, d_ref_len: n_refs int64; d_work: 16-byte aligned, work_bytes >=
+ * bc_bam_select_bytes.  BC_E_ARG before any device is touched: NULL pointer, negative n or n_refs,
+ * n >= 2^31, small or misaligned work buffer, n_cap < n or ref_cap < n_refs.                    */
+int bc_bam_select(bc_ctx* ctx, const bc_bam_arrays* d_rec, int64_t n, int64_t min_mapq, const uint8_t* d_ref_sel,
+                  const int64_t* d_ref_len, int32_t n_refs, void* d_work, size_t work_bytes, const bc_sel_arrays* d_out);
+
 /* ---- Multi-GPU: one process per GPU, RCCL over xGMI ---------------------------
  * Counting needs no exchange: references are independent, so each rank owns whole references
  * and runs the single-GPU path on them.  What crosses GPUs is small: the per-reference results
