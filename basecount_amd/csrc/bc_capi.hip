@@ -800,6 +800,43 @@ int bc_bam_select(bc_ctx* c, const bc_bam_arrays* r, int64_t n, int64_t min_mapq
     return BC_OK;
 }
 
+// ---- row formatting on the device (bc_fmt.hip) ----
+namespace {
+const char* fmt_size_error(int64_t n, int64_t n_seg) {
+    if (n < 0 || n_seg < 0) return "negative n or n_seg";
+    if (n > 0x7FFFFFFFll) return "n must be below 2^31";
+    if (n_seg < 1) return "n_seg must be at least 1";
+    if (n_seg > 0x7FFFFFFFll) return "n_seg must be below 2^31";
+    return nullptr;
+}
+}  // namespace
+
+int bc_fmt_rows_bytes(int64_t n, int64_t n_seg, size_t* work_bytes, size_t* out_small_bytes) {
+    if (!work_bytes || !out_small_bytes) return fail(BC_E_ARG, "bc_fmt_rows_bytes: NULL pointer");
+    if (const char* m = fmt_size_error(n, n_seg)) return fail(BC_E_ARG, std::string("bc_fmt_rows_bytes: ") + m);
+    *work_bytes = bc::fmt_work_bytes(n);
+    *out_small_bytes = 64u + 8u * ((size_t)n_seg + 1u);
+    return BC_OK;
+}
+
+int bc_fmt_rows(bc_ctx* c, const bc_fmt_args* a, void* d_work, size_t work_bytes, void* d_out, uint8_t* d_text,
+                int64_t text_cap) {
+    if (!c) return fail(BC_E_ARG, "ctx is NULL");
+    if (!a || !d_work || !d_out || !d_text) return fail(BC_E_ARG, "bc_fmt_rows: NULL pointer");
+    if (!a->counts || !a->pc || !a->ent || !a->sec || !a->segs || !a->names)
+        return fail(BC_E_ARG, "bc_fmt_rows: NULL pointer among the arguments' arrays");
+    if (a->k != 5 && a->k != 6) return fail(BC_E_ARG, "bc_fmt_rows: k must be 5 or 6");
+    if (a->dp < 0 || a->dp > 4) return fail(BC_E_ARG, "bc_fmt_rows: dp must lie in [0, 4]");
+    if (const char* m = fmt_size_error(a->n, a->n_seg)) return fail(BC_E_ARG, std::string("bc_fmt_rows: ") + m);
+    if (a->names_bytes < 0 || text_cap < 0) return fail(BC_E_ARG, "bc_fmt_rows: negative names_bytes or text_cap");
+    if (a->stride < a->n) return fail(BC_E_ARG, "bc_fmt_rows: stride must be at least n");
+    if (work_bytes < bc::fmt_work_bytes(a->n)) return fail(BC_E_ARG, "bc_fmt_rows: d_work smaller than bc_fmt_rows_bytes");
+    if (((uintptr_t)d_work | (uintptr_t)d_out) & 7u) return fail(BC_E_ARG, "bc_fmt_rows: d_work and d_out must be 8-byte aligned");
+    DeviceGuard g(c->device);
+    HIP_TRY(bc::launch_fmt_rows(c->stream, *a, d_work, d_out, d_text, text_cap));
+    return BC_OK;
+}
+
 int bc_ctx_stream(bc_ctx* c, void** s) {
     if (!c || !s) return fail(BC_E_ARG, "NULL argument");
     *s = (void*)c->stream;

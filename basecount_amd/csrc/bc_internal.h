@@ -214,4 +214,9 @@ size_t select_bytes(int64_t n, int64_t n_refs);
 hipError_t launch_select(hipStream_t s, const bc_bam_arrays& rec, int64_t n, int64_t min_mapq, const uint8_t* ref_sel,
                          const int64_t* ref_len, int32_t n_refs, void* work, const bc_sel_arrays& out);
 
+// ---- row formatting (bc_fmt.hip over bc_fmt.h): the argument limits are the caller's check ----
+size_t fmt_work_bytes(int64_t n);
+hipError_t launch_fmt_rows(hipStream_t s, const bc_fmt_args& args, void* work, void* out, uint8_t* text,
+                           int64_t text_cap);
+
 }  // namespace bc

@@ -131,6 +131,48 @@ def bam_select_bytes(n: int, n_refs: int) -> int:
     return int(b.value)
 
 
+class BcFmtArgs(C.Structure):
+    """bc_fmt_args: the device arrays bc_fmt_rows prints and the segment table that says how."""
+    _fields_ = [("counts", C.c_void_p), ("pc", C.c_void_p), ("ent", C.c_void_p), ("sec", C.c_void_p),
+                ("stride", C.c_int64), ("n", C.c_int64), ("segs", C.c_void_p), ("n_seg", C.c_int64),
+                ("names", C.c_void_p), ("names_bytes", C.c_int64), ("k", C.c_int32), ("dp", C.c_int32),
+                ("long_format", C.c_int32), ("reserved", C.c_int32)]
+
+
+FMT_HEADER_DTYPE = np.dtype([("status", "<i4"), ("reserved0", "<i4"), ("total_bytes", "<i8"), ("declined_pos", "<i8"),
+                             ("reserved", "<i8", (5,))])  # bc_fmt_header, 64 bytes
+FMT_SEG_DTYPE = np.dtype([("beg", "<i8"), ("len", "<i8"), ("pos0", "<i8"), ("name_off", "<i4"),
+                          ("name_len", "<i4")])  # bc_fmt_seg, 32 bytes
+FMT_STATUS = ("ok", "too_small", "value")  # BC_FMT_*
+FMT_OK, FMT_TOO_SMALL, FMT_VALUE = 0, 1, 2
+FMT_MAX_DP, FMT_MAX_NAME = 4, 255
+
+
+def fmt_supported(dp: int, names) -> bool:
+    """Whether bc_fmt_rows covers these decimal places and reference names (printed values outside its
+    cover are found by the kernels: BC_FMT_VALUE)."""
+    return 0 <= int(dp) <= FMT_MAX_DP and all(len(n.encode()) <= FMT_MAX_NAME for n in names)
+
+
+def fmt_rows_bytes(n: int, n_seg: int) -> tuple:
+    """bc_fmt_rows_bytes: (bytes of the work buffer, bytes of the header + seg_off)."""
+    w, o = C.c_size_t(0), C.c_size_t(0)
+    check(lib().bc_fmt_rows_bytes(int(n), int(n_seg), C.byref(w), C.byref(o)))
+    return int(w.value), int(o.value)
+
+
+def fmt_table(segs) -> tuple:
+    """The segment table and the names array of bc_fmt_rows from (beg, len, pos0, name) tuples."""
+    tab = np.zeros(len(segs), FMT_SEG_DTYPE)
+    blob, at = [], 0
+    for i, (beg, ln, pos0, name) in enumerate(segs):
+        b = name if isinstance(name, bytes) else name.encode()
+        tab[i] = (beg, ln, pos0, at, len(b))
+        blob.append(b)
+        at += len(b)
+    return tab, np.frombuffer(b"".join(blob) + b"\0", np.uint8)
+
+
 BAM_STATUS = ("ok", "partial_len", "partial", "short", "neg_lseq", "fields", "too_large", "repairs", "internal")  # BC_BAM_*
 
 
@@ -238,6 +280,9 @@ def lib() -> C.CDLL:
         "bc_bam_select_bytes": ([i64, i64, C.POINTER(C.c_size_t)], C.c_int),
         "bc_bam_select": ([vp, C.POINTER(BcBamArrays), i64, i64, vp, vp, C.c_int32, vp, C.c_size_t,
                            C.POINTER(BcSelArrays)], C.c_int),
+        # row formatting on the device (bc_fmt.hip)
+        "bc_fmt_rows_bytes": ([i64, i64, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)], C.c_int),
+        "bc_fmt_rows": ([vp, C.POINTER(BcFmtArgs), vp, C.c_size_t, vp, vp, i64], C.c_int),
         # multi-GPU (bc_comm.hip)
         "bc_comm_unique_id": ([vp], C.c_int),
         "bc_comm_init": ([vp, vp, C.c_int, C.c_int, C.POINTER(vp)], C.c_int),
@@ -579,6 +624,12 @@ class Context:
         mmq = max(min(int(min_mapq), 1 << 40), -(1 << 40))
         check(lib().bc_bam_select(self.h, C.byref(rec), int(n), mmq, d_ref_sel, d_ref_len, int(n_refs), d_work,
                                   int(work_bytes), C.byref(out)))
+
+    def fmt_rows(self, args: BcFmtArgs, d_work: int, work_bytes: int, d_out: int, d_text: int, text_cap: int) -> None:
+        """bc_fmt_rows: the TSV rows of device-resident outputs into d_text, stream-ordered (capturable,
+        no allocation).  d_out: the 64-byte header (FMT_HEADER_DTYPE) and seg_off[n_seg + 1]; the
+        header's status says whether the text is to be used."""
+        check(lib().bc_fmt_rows(self.h, C.byref(args), d_work, int(work_bytes), d_out, d_text, int(text_cap)))
 
     def capture(self, fn) -> "Graph":
         """Record the compute calls made by fn() into a hipGraph (replay with Graph.launch)."""

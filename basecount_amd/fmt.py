@@ -75,7 +75,7 @@ def write_bytes(data: bytes) -> None:
         buf.write(data)
         buf.flush()
     else:
-        out.write(data.decode())
+        out.write(bytes(data).decode())  # (bytes-like: the device formatter hands out views)
 
 
 def pyround_native(x: float, dp: int) -> str:

@@ -95,6 +95,14 @@ def device_select_on() -> bool:
     return os.environ.get("BASECOUNT_DEVICE_SELECT") not in (None, "", "0")
 
 
+# BASECOUNT_DEVICE_FORMAT=1: the CLI's rows are written on the device ("Device row
+# formatting"): bc_fmt_rows turns the counts, percentages and entropies into the TSV text where the
+# kernels left them, and the host downloads a header, the segment offsets and the text instead of
+# five arrays per reference.  Independent of the input switches; unsharded rows runs only.
+def device_format_on() -> bool:
+    return os.environ.get("BASECOUNT_DEVICE_FORMAT") not in (None, "", "0")
+
+
 _DECODE_MS = {"fills": 0, "upload_ms": 0.0, "inflate_ms": 0.0, "index_ms": 0.0, "fill_ms": 0.0, "download_ms": 0.0,
               "fill_wall_ms": 0.0, "next_wall_ms": 0.0}
 
@@ -264,6 +272,7 @@ class _Scratch:
     def __init__(self, ctx):
         self.ctx, self.bufs = ctx, {}
         self.pending_sort = None  # (unsorted reads, sort memory) whose device flags are unread
+        self.formatter = None  # BASECOUNT_DEVICE_FORMAT: the call's _DeviceFormatter (rows as text)
 
     def check_sort(self):
         """The flags of the last device sort (bc_reads_sort_check), read once the reference's
@@ -841,6 +850,116 @@ def _reads_inside(pos, span, ref_beg, lengths_t) -> np.ndarray:
     return ok
 
 
+FORMAT_SLICE = 1 << 22  # array positions of one bc_fmt_rows call: the text buffer stays bounded
+_FORMAT_MS = {"calls": 0, "device_ms": 0.0, "download_ms": 0.0, "text_bytes": 0, "retries": 0}
+FORMAT_TIMING = False  # event pairs around bc_fmt_rows without BASECOUNT_HIP_TIMING (scripts/format_bench.py)
+
+
+class _DeviceFormatter:
+    """bc_fmt_rows on a call's outputs where the kernels left them (``scratch``'s buffers): the
+    text of one reference (in slices of FORMAT_SLICE positions) or of a group's references, as
+    bytes-like objects (views of the downloaded buffer); None when the kernels declined a value
+    (the caller downloads the arrays as ever).
+    ``name`` / ``names``: what the next outputs are printed under, set by the call's loop."""
+
+    def __init__(self, ctx, scratch, k, dp, long_format):
+        self.ctx, self.scratch, self.k, self.dp, self.long = ctx, scratch, int(k), int(dp), bool(long_format)
+        self.name, self.names = None, None
+        self.per_pos = 0.0  # text bytes per position seen so far (the next buffer's estimate)
+        self.timing = bool(os.environ.get("BASECOUNT_HIP_TIMING")) or FORMAT_TIMING
+        self.plan = PLAN["format"]  # the call's routing: the declined references are named here
+
+    def _estimate(self, segs, n) -> int:
+        """Bytes the text of these segments is likely to take: five-digit counts, percentages below
+        100; a larger text is found by the kernels (BC_FMT_TOO_SMALL) and formatted again."""
+        k, dp = self.k, self.dp
+        est = 0
+        for _, ln, pos0, name in segs:
+            head = len(name.encode()) + 1 + len(str(pos0 + ln)) + 1 + 6
+            vals = 2 * (dp + 4) + 1
+            row = k * (head + 3 + 6 + dp + 4 + vals) if self.long else head + k * (6 + dp + 4) + vals
+            est += ln * row
+        return max(int(est * 1.1), int(n * self.per_pos * 1.1)) + 4096
+
+    def _call(self, segs, d_counts, d_pc, d_ent, d_sec, stride, n):
+        """(text as uint8, seg_off) of one bc_fmt_rows call, or (None, declined position)."""
+        import time
+
+        ctx, sc = self.ctx, self.scratch
+        tab, names = D.fmt_table(segs)
+        blob = np.concatenate([tab.view(np.uint8), names])
+        d_tab = sc.get("fmt_table", blob.nbytes).upload(blob)
+        wb, ob = D.fmt_rows_bytes(n, len(segs))
+        work, out = sc.get("fmt_work", wb), sc.get("fmt_out", ob)
+        a = D.BcFmtArgs()
+        a.counts, a.pc, a.ent, a.sec = d_counts, d_pc, d_ent, d_sec
+        a.stride, a.n, a.segs, a.n_seg = int(stride), int(n), d_tab.ptr, len(segs)
+        a.names, a.names_bytes = d_tab.ptr + tab.nbytes, int(names.size)
+        a.k, a.dp, a.long_format = self.k, self.dp, int(self.long)
+        cap = self._estimate(segs, n)
+        for attempt in (0, 1):
+            text = sc.get("fmt_text", cap)
+            if self.timing:
+                ctx.event_record(0)
+            ctx.fmt_rows(a, work.ptr, work.nbytes, out.ptr, text.ptr, text.nbytes)
+            if self.timing:
+                ctx.event_record(1)
+            small = out.download(np.uint8, ob)  # (synchronises: the text is complete)
+            if self.timing:
+                _FORMAT_MS["calls"] += 1
+                _FORMAT_MS["device_ms"] += ctx.event_elapsed_ms(0, 1)
+            h = small[:64].view(D.FMT_HEADER_DTYPE)[0]
+            status, total = int(h["status"]), int(h["total_bytes"])
+            if status != D.FMT_TOO_SMALL or attempt:
+                break
+            cap = total  # once more, at the exact size
+            _FORMAT_MS["retries"] += 1
+        if status != D.FMT_OK:
+            return None, int(h["declined_pos"])
+        t0 = time.perf_counter()
+        body = text.download(np.uint8, total)
+        _FORMAT_MS["download_ms"] += (time.perf_counter() - t0) * 1e3
+        _FORMAT_MS["text_bytes"] += total
+        if n:
+            self.per_pos = max(self.per_pos, total / n)
+        return body, small[64:].view(np.int64)
+
+    def reference(self, hist, outs, L):
+        """The text of reference ``name`` from its outputs of L positions, or None."""
+        parts = []
+        for s in range(0, L, FORMAT_SLICE):
+            n = min(FORMAT_SLICE, L - s)
+            body, _ = self._call([(0, n, s, self.name)], hist.ptr + 4 * s, outs["pc"].ptr + 8 * s,
+                                 outs["ent"].ptr + 8 * s, outs["sec"].ptr + 8 * s, L, n)
+            if body is None:
+                self.plan["declined"].append(self.name)
+                return None
+            parts.append(memoryview(body))  # (the downloaded buffer itself: no copy of the text)
+        return parts[0] if len(parts) == 1 else b"".join(parts)
+
+    def group(self, lens, voff, hist, outs, Lv) -> list:
+        """The texts of a group's references ``names`` (None for those of a run of references that
+        holds a declined value), in runs of at most FORMAT_SLICE virtual positions."""
+        res, i, n = [], 0, len(lens)
+        while i < n:
+            j, v0 = i + 1, int(voff[i])
+            while j < n and int(voff[j]) + int(lens[j]) - v0 <= FORMAT_SLICE:
+                j += 1
+            span = int(voff[j - 1]) + int(lens[j - 1]) - v0
+            segs = [(int(voff[t]) - v0, int(lens[t]), 0, self.names[t]) for t in range(i, j)]
+            body, off = self._call(segs, hist.ptr + 4 * v0, outs["pc"].ptr + 8 * v0, outs["ent"].ptr + 8 * v0,
+                                   outs["sec"].ptr + 8 * v0, Lv, span)
+            if body is None:
+                bad = [t for t in range(i, j) if int(voff[t]) - v0 <= off < int(voff[t]) - v0 + int(lens[t])]
+                self.plan["declined"].extend(self.names[t] for t in bad)
+                res.extend([None] * (j - i))
+            else:
+                raw = memoryview(body)
+                res.extend(raw[int(off[t]):int(off[t + 1])] for t in range(j - i))
+            i = j
+        return res
+
+
 def _device_group(ctx, reads, lens, read_beg, mbq, k, nf, nf2, mode, scratch) -> list:
     """One launch and one download per output array for a group of references (their lengths
     ``lens``; reads [read_beg[i], read_beg[i + 1]) of ``reads`` are reference i's): each
@@ -862,10 +981,18 @@ def _device_group(ctx, reads, lens, read_beg, mbq, k, nf, nf2, mode, scratch) ->
         s = d_sum.download(np.float64, 4 * n).reshape(n, 4)
         return [{"L": int(L), "avg_cov": np.float64(s[i, 0]), "avg_ent": np.float64(s[i, 1]), "nnz": int(s[i, 2])}
                 for i, L in enumerate(lens)]
+    texts = [None] * n
+    if scratch.formatter is not None:  # the text where the arrays lie; None: a declined value
+        texts = scratch.formatter.group(lens, voff, hist, outs, Lv)
+        if all(t is not None for t in texts):
+            return texts
     counts = hist.download(np.int32, k * Lv).reshape(k, Lv)
     d = _download(outs, counts, k, Lv)
     out = []
     for i, L in enumerate(lens):
+        if texts[i] is not None:
+            out.append(texts[i])
+            continue
         sl = slice(int(voff[i]), int(voff[i]) + int(L))
         out.append(RefData(np.ascontiguousarray(d.counts[:, sl]), np.ascontiguousarray(d.pc[:, sl]),
                            d.ent[sl].copy(), d.sec[sl].copy(), d.cov[sl].copy()))
@@ -906,10 +1033,13 @@ def _shard_decode_on(group) -> bool:
 
 def get_basecounts(bam, references=None, min_base_quality=0, min_mapping_quality=0,
                    chunk_size=1000000, show_n_bases=False, long_format=False, *, device=None,
-                   _mode="rows", _tiles=None, _group=None, _keep_scratch=False):
+                   _mode="rows", _tiles=None, _group=None, _keep_scratch=False, _dp=None):
     """main.py:110-205 on the device.  Returns {ref: {"rows": Rows, "num_reads": n}} in the
     reference's (set) order.  ``_mode="summary"`` keeps per-position data in HBM and returns
-    the numpy-exact summary (and amplicon) reductions instead of rows.
+    the numpy-exact summary (and amplicon) reductions instead of rows.  ``_mode="text"`` (the CLI
+    under BASECOUNT_DEVICE_FORMAT) returns {ref: {"text": bytes-like, "num_reads": n}}: each reference's
+    rows as the TSV body with ``_dp`` decimal places, written on the device where bc_fmt_rows covers
+    them (an unsharded run, D.fmt_supported) and by fmt.rows_text otherwise.
 
     The BAM streams through in batches of records (``batch_records(chunk_size)``, the
     reference's chunked read loop): host and HBM memory hold one batch (two while the next is
@@ -927,9 +1057,13 @@ def get_basecounts(bam, references=None, min_base_quality=0, min_mapping_quality
     PLAN["inflate"] = {"device": 0, "host": 0}  # BGZF blocks inflated by k_inflate / on the host
     PLAN["decode"] = {"device": 0, "host": 0, "repaired": 0}  # fills decoded on the device / declined to the host
     PLAN.pop("select", None)  # BASECOUNT_DEVICE_SELECT: batches selected on the device / on the host (set by the run)
+    PLAN.pop("format", None)  # _mode="text": references formatted on the device / on the host (set by the run)
+    dp = None
+    if _mode == "text":  # rows all the way, printed at the end of the call
+        _mode, dp = "rows", int(_dp)
     try:
         return _get_basecounts_top(bam, references, min_base_quality, min_mapping_quality, chunk_size,
-                                   show_n_bases, long_format, device, _mode, _tiles, _group)
+                                   show_n_bases, long_format, device, _mode, _tiles, _group, dp)
     finally:
         if _keep_scratch:
             _KEPT.update(_SCRATCHES)
@@ -938,13 +1072,13 @@ def get_basecounts(bam, references=None, min_base_quality=0, min_mapping_quality
 
 
 def _get_basecounts_top(bam, references, min_base_quality, min_mapping_quality, chunk_size, show_n_bases,
-                        long_format, device, _mode, _tiles, _group):
+                        long_format, device, _mode, _tiles, _group, dp=None):
     args = (bam, references, min_base_quality, min_mapping_quality, chunk_size, show_n_bases,
             long_format, device, _mode, _tiles, _group)
     if _shard_decode_on(_group):
         # each rank inflates and decodes only the byte range of its own references (a file
         # grouped by reference); None: some rank's range did not confirm, all decode everything
-        res = _get_basecounts(*args, grouped=True, sharded=True)
+        res = _get_basecounts(*args, grouped=True, sharded=True, dp=dp)
         if res is not None:
             return res
         if os.environ.get("BASECOUNT_SHARD_DECODE") == "require":  # tests: the split must hold
@@ -953,18 +1087,19 @@ def _get_basecounts_top(bam, references, min_base_quality, min_mapping_quality, 
             print(f"basecount[{_group.rank}] sharded decode missed: every rank decodes the file",
                   file=sys.stderr)
     try:
-        res = _get_basecounts(*args, grouped=True)
+        res = _get_basecounts(*args, grouped=True, dp=dp)
     except _Ungrouped:  # (one process: raised where the reference came back)
         res = _UNGROUPED
     if res is _UNGROUPED:  # with a group, every rank returns it (the ranks vote after the loop)
-        return _get_basecounts(*args, grouped=False)
+        return _get_basecounts(*args, grouped=False, dp=dp)
     return res
 
 
 def _get_basecounts(bam, references, min_base_quality, min_mapping_quality, chunk_size, show_n_bases,
-                    long_format, device, _mode, _tiles, _group, grouped, sharded=False):
+                    long_format, device, _mode, _tiles, _group, grouped, sharded=False, dp=None):
     stream = _open_stream(bam, device)
     selector = None  # BASECOUNT_DEVICE_SELECT: the device-decoded batches of an unsharded run
+    fm = None  # BASECOUNT_DEVICE_FORMAT: the rows of an unsharded run as text (dp: its decimal places)
     try:
         references = get_references(stream, references)
         names = stream.references
@@ -1045,6 +1180,10 @@ def _get_basecounts(bam, references, min_base_quality, min_mapping_quality, chun
         # reference, for rows and plain --summarise (the amplicon windows keep the per-reference path)
         cap = group_cap() if (ctx is not None and grouped and _tiles is None) else 0
         PLAN["groups"], PLAN["single"], PLAN["ops"] = [], [], []
+        if dp is not None:
+            PLAN["format"] = {"device": 0, "host": 0, "declined": []}
+            if ctx is not None and _group is None and _mode == "rows" and D.fmt_supported(dp, ref_order):
+                fm = scratch.formatter = _DeviceFormatter(ctx, scratch, k, dp, long_format)
 
         def tiles_of(ref):
             return _tiles(ref) if _tiles else None
@@ -1083,6 +1222,8 @@ def _get_basecounts(bam, references, min_base_quality, min_mapping_quality, chun
         def run_group(tids, reads, read_beg, ops=None):
             if ops is None:  # a group without reads
                 ops = wants_ops(())
+            if fm is not None:
+                fm.names = [names[t] for t in tids]
             with _ops_shape(ctx, ops):
                 res = _device_group(ctx, reads, [int(lens_t[t]) for t in tids], read_beg, mbq, k, nf, nf2, _mode,
                                     scratch)
@@ -1194,6 +1335,8 @@ def _get_basecounts(bam, references, min_base_quality, min_mapping_quality, chun
                         PLAN["single"].append(ref)
                         t = ref_index[ref]
                         L = int(reference_lengths[ref])
+                        if fm is not None:
+                            fm.name = ref
                         # (a reference split over ranks is never complete on one: accumulated)
                         closed = grouped and ref not in split and (
                             nxt is None or int(nsel.ref_beg[t + 1]) == int(nsel.ref_beg[t]))
@@ -1251,6 +1394,8 @@ def _get_basecounts(bam, references, min_base_quality, min_mapping_quality, chun
                         continue
                     PLAN["single"].append(ref)
                     L = int(reference_lengths[ref])
+                    if fm is not None:
+                        fm.name = ref
                     if ref in acc:
                         results[ref] = _finish_reference(ctx, acc.pop(ref), L, ncols, k, nf, nf2, _mode,
                                                          tiles_of(ref), _tiles is not None, scratch)
@@ -1318,7 +1463,13 @@ def _get_basecounts(bam, references, min_base_quality, min_mapping_quality, chun
         out = {}
         for ref in mine:
             n = nreads[ref]
-            if _mode == "rows":
+            if dp is not None:
+                r = results[ref]
+                PLAN["format"]["host" if isinstance(r, RefData) else "device"] += 1
+                if isinstance(r, RefData):  # not covered, declined or empty: the host formatter
+                    r = fmt.rows_text(ref, r.counts[:k], r.pc, r.ent, r.sec, dp, long_format)
+                out[ref] = {"text": r, "num_reads": n}
+            elif _mode == "rows":
                 out[ref] = {"rows": Rows(ref, results[ref], long_format), "num_reads": n}
             else:
                 out[ref] = {"summary": results[ref], "num_reads": n,
@@ -1327,6 +1478,8 @@ def _get_basecounts(bam, references, min_base_quality, min_mapping_quality, chun
             return out, owner, ref_order
         return out
     finally:
+        if fm is not None:
+            fm.scratch.formatter = None
         if selector is not None:
             selector.release()
         _note_inflate(stream)
@@ -1490,6 +1643,10 @@ def _collect(ctx, outs, hist, L, k, ncols, mode, tiles, want_tiles, scratch, sta
             nf, nf2 = norm_factors(k)
         ctx.stats(hist.ptr, L, k, nf, nf2, outs["cov"].ptr, pc_ptr, outs["ent"].ptr, outs["sec"].ptr)
     if mode == "rows":
+        if scratch.formatter is not None and ncols == k:
+            text = scratch.formatter.reference(hist, outs, L)
+            if text is not None:
+                return text
         counts = hist.download(np.int32, ncols * L).reshape(ncols, L)
         return _download(outs, counts, k, L)
     dout = scratch.get("dout", 32)
@@ -1757,6 +1914,11 @@ def _timing_report(wall_s: float) -> None:
     if _SELECT_MS["calls"]:  # BASECOUNT_DEVICE_SELECT=1: inside the select phase too
         print(f"basecount[{rank}] device select: {_SELECT_MS['calls']} batches, k_sel_count .. k_sel_facts "
               f"{_SELECT_MS['device_ms']:.3f} ms", file=sys.stderr)
+    if _FORMAT_MS["calls"]:  # BASECOUNT_DEVICE_FORMAT=1: inside the kernels + download phase
+        t = _FORMAT_MS
+        print(f"basecount[{rank}] device format: {t['calls']} calls ({t['retries']} repeated at the exact size), "
+              f"k_fmt_measure + k_fmt_scan + k_fmt_write {t['device_ms']:.3f} ms, text download {t['download_ms']:.2f} ms "
+              f"for {t['text_bytes']} bytes", file=sys.stderr)
     print(f"basecount[{rank}] wall {wall_s * 1e3:.2f} ms", file=sys.stderr)
 
 
@@ -1767,6 +1929,14 @@ def _run(args, references, min_base_quality, min_mapping_quality, chunk_size, be
               min_mapping_quality=min_mapping_quality, chunk_size=chunk_size,
               show_n_bases=args.show_n_bases, long_format=args.long_format)
     if (not args.summarise) and (bed is None):
+        if group is None and device_format_on():
+            # the rows as text, written on the device where bc_fmt_rows covers them
+            out = get_basecounts(args.bam, **kw, _mode="text", _dp=dp)
+            print("\t".join(_columns(args.show_n_bases, args.long_format)))
+            with _phase("format + write"):
+                for ref in out:
+                    fmt.write_bytes(out[ref]["text"])
+            return
         if group is None:
             bc = BaseCount(args.bam, **kw)
             print("\t".join(bc.columns))

@@ -654,7 +654,67 @@ int bc_bam_select_bytes(int64_t n, int64_t n_refs, size_t* bytes);
 int bc_bam_select(bc_ctx* ctx, const bc_bam_arrays* d_rec, int64_t n, int64_t min_mapq, const uint8_t* d_ref_sel,
                   const int64_t* d_ref_len, int32_t n_refs, void* d_work, size_t work_bytes, const bc_sel_arrays* d_out);
 
-/* ---- Multi-GPU: one process per GPU, RCCL over xGMI ---------------------------
+/* ---- Row formatting on the device (bc_fmt.hip over bc_fmt.h) ------------------------------------
+ * The TSV rows bcio_fmt_rows (bcio.h) writes, byte for byte, from the arrays the kernels left in
+ * HBM: counts int32 [k][.] and pc f64 [k][.] as planes of `stride` elements, ent and sec f64, n
+ * array positions.  A table of n_seg >= 1 segments, sorted by beg, says what prints: segment i is
+ * the array positions [beg, beg + len) with beg a multiple of 64, printed as positions pos0 + 1 ..
+ * under the name names[name_off, name_off + name_len); array positions outside every segment (the
+ * pads of bc_segments_layout) print nothing.  One reference is n_seg = 1 with beg = 0; a slice of a
+ * large reference passes pos0 > 0 and pointers offset to the slice.
+ * d_out receives a 64-byte bc_fmt_header followed by seg_off[n_seg + 1] (int64): segment i's text is
+ * the bytes [seg_off[i], seg_off[i + 1]) of d_text.
+ * Declined, never failed.  BC_FMT_VALUE: a printed value is not finite or reaches 1e15 after scaling
+ * by 10^dp, or a name is longer than 255 bytes or leaves the names array; declined_pos is the first
+ * such array position.  BC_FMT_TOO_SMALL: total_bytes > text_cap; total_bytes and seg_off are
+ * exact, so the call can be repeated with a buffer of that size.  BC_FMT_VALUE wins when both hold.
+ * The call returns BC_OK in either case and no text byte is to be trusted.  Whatever the arrays and
+ * the table hold, nothing is read past n positions or the names array, nothing is written at or
+ * past min(total_bytes, text_cap).                                                               */
+#define BC_FMT_OK 0
+#define BC_FMT_TOO_SMALL 1
+#define BC_FMT_VALUE 2
+
+typedef struct bc_fmt_header {
+    int32_t status;        /* BC_FMT_* */
+    int32_t reserved0;
+    int64_t total_bytes;
+    int64_t declined_pos;  /* -1 without one */
+    int64_t reserved[5];
+} bc_fmt_header;
+
+typedef struct bc_fmt_seg {
+    int64_t beg, len, pos0;
+    int32_t name_off, name_len;
+} bc_fmt_seg;
+
+typedef struct bc_fmt_args {
+    const int32_t* counts;   /* device pointers */
+    const double* pc;
+    const double* ent;
+    const double* sec;
+    int64_t stride;          /* elements between the planes of counts and of pc, >= n */
+    int64_t n;               /* array positions, 0 <= n < 2^31 */
+    const bc_fmt_seg* segs;  /* device, n_seg entries */
+    int64_t n_seg;
+    const uint8_t* names;    /* device, names_bytes bytes */
+    int64_t names_bytes;
+    int32_t k;               /* 5 or 6 columns printed */
+    int32_t dp;              /* decimal places, 0 .. 4 */
+    int32_t long_format;
+    int32_t reserved;
+} bc_fmt_args;
+
+/* Host arithmetic: the bytes of d_work and of d_out (the header and seg_off) for n positions and
+ * n_seg segments.                                                                                */
+int bc_fmt_rows_bytes(int64_t n, int64_t n_seg, size_t* work_bytes, size_t* out_small_bytes);
+/* Stream-ordered, no allocation, no synchronisation: capturable.  d_work and d_out: 8-byte aligned.
+ * BC_E_ARG before any device is touched: NULL pointer, k not 5 or 6, dp outside [0, 4], negative
+ * sizes, n >= 2^31, n_seg < 1, stride < n, a work buffer smaller than bc_fmt_rows_bytes.         */
+int bc_fmt_rows(bc_ctx* ctx, const bc_fmt_args* args, void* d_work, size_t work_bytes, void* d_out, uint8_t* d_text,
+                int64_t text_cap);
+
+/* ---- Multi-GPU: one process per GPU, RCCL over xGMI---------------------------
  * Counting needs no exchange: references are independent, so each rank owns whole references
  * and runs the single-GPU path on them.  What crosses GPUs is small: the per-reference results
  * the reference prints (main.py:469-595) gathered to rank 0, the reference order rank 0 chose
