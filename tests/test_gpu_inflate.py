@@ -1,7 +1,7 @@
 """k_inflate through bc_bgzf_inflate against zlib: the vectors of tests/inflate_vectors.py packed back
 to back (unaligned coff / uoff), sentinel guards around input and output and between the blocks.
-The invalid list is a bounds check of a correct kernel under the rule "status 0 => zlib accepts and
-the bytes are equal"; the host sanitizer program (tests/test_inflate_host.py) runs the same header
+The invalid list is a bounds check of a correct kernel under the contract's equivalence "status 0
+exactly where zlib accepts, and then the same bytes"; the host sanitizer program (tests/test_inflate_host.py) runs the same header
 on the same vectors."""
 import numpy as np
 import pytest
@@ -96,7 +96,7 @@ def test_invalid_vectors_obey_the_rule(ctx):
     check(V.INVALID, blocks, out, status, False)
     assert np.count_nonzero(status) > len(V.INVALID) // 2
     by = dict(zip((x.name for x in V.INVALID), status))
-    for name in ("distance_before_start", "btype3", "stored_bad_nlen"):
+    for name in V.NAMED_INVALID:
         assert by[name] != 0, name
 
 
@@ -126,6 +126,18 @@ def test_host_entry_point_matches(ctx):
     check(V.VALID, blocks, out, status, True)
     t = ctx.bgzf_inflate_times()
     assert t["blocks"] >= len(blocks) and t["kernel_ms"] > 0
+
+
+def test_host_entry_point_inflates_the_fuzz_streams(ctx):
+    """The structured fuzz streams (random code sets, headers and block mixes) once more, through
+    bc_bgzf_inflate_host and in reverse order: other neighbours, other alignments."""
+    by = {x.name: x for x in V.VALID}
+    vecs = [by[name] for name in reversed(V.FUZZ_NAMES)]
+    assert len(vecs) >= 300
+    comp, out0, blocks = pack(vecs)
+    out = out0.copy()
+    status = ctx.bgzf_inflate_host(comp, blocks, out)
+    check(vecs, blocks, out, status, True)
 
 
 def test_host_entry_point_refuses_bad_descriptors(ctx):

@@ -53,6 +53,7 @@ def test_valid_streams_inflate_to_zlibs_bytes(results):
 
 
 def test_invalid_streams_never_accepted_unless_zlib_accepts(results):
+    """Both directions (V.check_rule): refused where zlib refuses, zlib's bytes where it accepts."""
     refused = 0
     for x in V.INVALID:
         status, guards, out = results[x.name]
@@ -63,5 +64,5 @@ def test_invalid_streams_never_accepted_unless_zlib_accepts(results):
 
 
 def test_named_invalid_streams_are_refused(results):
-    for name in ("distance_before_start", "btype3", "stored_bad_nlen"):
+    for name in V.NAMED_INVALID:
         assert results[name][0] != 0, name
