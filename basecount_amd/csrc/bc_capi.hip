@@ -865,6 +865,26 @@ int bc_pileup_plan(const bc_reads* r, int64_t ref_len, int shape, int tile_waves
     return BC_OK;
 }
 
+int bc_ctx_set_instance(bc_ctx* c, int instance) {
+    if (!c) return fail(BC_E_ARG, "ctx is NULL");
+    if (instance < BC_INSTANCE_AUTO || instance > BC_INSTANCE_LEAN) return fail(BC_E_ARG, "unknown BC_INSTANCE_* value");
+    c->instance = instance;
+    return BC_OK;
+}
+
+int bc_pileup_launch_info(const bc_reads* r, int64_t ref_len, int shape, int tile_waves, int instance, uint32_t mbq,
+                          int k, bc_launch_info* out) {
+    if (!r || !out) return fail(BC_E_ARG, "NULL argument");
+    if (r->n_reads < 0 || ref_len < 0) return fail(BC_E_ARG, "bc_pileup_launch_info: n_reads or ref_len < 0");
+    if (shape < BC_SHAPE_AUTO || shape > BC_SHAPE_OPS) return fail(BC_E_ARG, "unknown BC_SHAPE_* value");
+    if (tile_waves != 0 && tile_waves != 1 && tile_waves != 2 && tile_waves != 4 && tile_waves != 8)
+        return fail(BC_E_ARG, "tile_waves must be 0, 1, 2, 4 or 8");
+    if (instance < BC_INSTANCE_AUTO || instance > BC_INSTANCE_LEAN) return fail(BC_E_ARG, "unknown BC_INSTANCE_* value");
+    if (k != 5 && k != 6) return fail(BC_E_ARG, "k must be 5 or 6");
+    bc::pileup_launch_info(*r, ref_len, shape, tile_waves, instance, mbq, k, *out);
+    return BC_OK;
+}
+
 int bc_sync(bc_ctx* c) {
     if (!c) return fail(BC_E_ARG, "ctx is NULL");
     DeviceGuard g(c->device);
@@ -1120,7 +1140,7 @@ int bc_count(bc_ctx* c, const bc_reads* r, int64_t ref_len, uint32_t mbq, int nc
         Timed tm(c, bc::pileup_is_solo(*r, ref_len, c->shape, c->tile_waves) ? BC_K_SOLO : BC_K_PILEUP);
         HIP_TRY(bc::launch_pileup_tiles(c->stream, *r, ref_len, r->max_end, mbq, ncols, false, true, 0.0, 0.0,
                                         d_hist, nullptr, nullptr, nullptr, nullptr, c->d_err, c->shape,
-                                        c->tile_waves));
+                                        c->tile_waves, c->instance));
         return BC_OK;
     }
     const int rpb = choose_rpb(r->n_reads, ref_len, r->max_span, r->sorted, c->reads_per_block);
@@ -1165,7 +1185,7 @@ int bc_pileup(bc_ctx* c, const bc_reads* r, int64_t L, uint32_t mbq, int k, doub
     }
     Timed tm(c, bc::pileup_is_solo(*r, L, c->shape, c->tile_waves) ? BC_K_SOLO : BC_K_PILEUP);
     HIP_TRY(bc::launch_pileup_tiles(c->stream, *r, L, r->max_end, mbq, k, true, false, nf, nf2, d_counts, d_cov,
-                                    d_pc, d_ent, d_sec, c->d_err, c->shape, c->tile_waves));
+                                    d_pc, d_ent, d_sec, c->d_err, c->shape, c->tile_waves, c->instance));
     return BC_OK;
 }
 
@@ -1260,7 +1280,7 @@ int bc_pileup_partials(bc_ctx* c, const bc_reads* r, int64_t L, uint32_t mbq, in
                 Timed tm(c, BC_K_SOLO);
                 HIP_TRY(bc::launch_pileup_tiles(c->stream, *r, L, r->max_end, mbq, k, true, false, nf, nf2, nullptr,
                                                 nullptr, nullptr, nullptr, nullptr, c->d_err, c->shape, c->tile_waves,
-                                                &parts));
+                                                c->instance, &parts));
             }
 #else
             {
@@ -1332,7 +1352,7 @@ int bc_pileup_partials(bc_ctx* c, const bc_reads* r, int64_t L, uint32_t mbq, in
     {
         Timed tm(c, bc::pileup_is_solo(*r, L, c->shape, c->tile_waves) ? BC_K_SOLO : BC_K_PILEUP);
         HIP_TRY(bc::launch_pileup_tiles(c->stream, *r, L, r->max_end, mbq, k, true, false, nf, nf2, d_counts, d_cov,
-                                        d_pc, d_ent, d_sec, c->d_err, c->shape, c->tile_waves, &parts));
+                                        d_pc, d_ent, d_sec, c->d_err, c->shape, c->tile_waves, c->instance, &parts));
     }
     const int64_t first = parts.fused ? parts.full_chunks : 0;
     Timed tm(c, BC_K_SUMMARY);  // the last, partial buffer (or all of them), and the header

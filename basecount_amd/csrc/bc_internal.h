@@ -39,6 +39,7 @@ struct bc_ctx {
     int shape = BC_SHAPE_AUTO;
     int tile_waves = 0;
     int reads_per_block = 0;
+    int instance = BC_INSTANCE_AUTO;  // k_pileup's instance (bc_ctx_set_instance)
 };
 
 // Diagnostic work-skipping switches (BC_ABLATE) exist only in -DBC_DIAG builds
@@ -98,7 +99,16 @@ struct SumParts {
 hipError_t launch_pileup_tiles(hipStream_t s, const bc_reads& r, int64_t L, int64_t max_end, uint32_t mbq, int k,
                                bool stats, bool accumulate, double nf, double nf2, int32_t* counts, int32_t* cov,
                                double* pc, double* ent, double* sec, unsigned long long* d_err, int shape = 0,
-                               int tile_waves = 0, SumParts* parts = nullptr);
+                               int tile_waves = 0, int instance = 0, SumParts* parts = nullptr);
+// instance: BC_INSTANCE_*; AUTO takes k_pileup's lean instance while the bound on the batch's
+// multi-run reads, (n_cigar_words - n_reads) / 2, is at most this share of its reads.  Measured
+// (scripts/lean_fraction.py): the lean instance is 10 % ahead with
+// no slow read and already 4 % behind with one read in 64 carrying an indel, so the share is zero:
+// only a batch whose reads all have ONE CIGAR op takes it.
+constexpr double kLeanMaxSlowShare = 0.0;
+// bc_pileup_launch_info: the instance launch_pileup_tiles launches (no pointer of r is read)
+void pileup_launch_info(const bc_reads& r, int64_t L, int shape, int tile_waves, int instance, uint32_t mbq, int k,
+                        bc_launch_info& out);
 // Summary only (main.py:469-499) for a sparse sorted batch: the read-parallel summary (counted
 // positions per 128-position leaf, exact walks of the leaves two reads share; k_sum_buffers adds
 // each 8192-position buffer's 64 leaves in numpy's tree order) into WHOLE-buffer partials

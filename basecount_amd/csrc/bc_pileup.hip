@@ -133,8 +133,11 @@ __device__ __forceinline__ void tile_tail(const ARGS& A, lds_u32* f, lds_f64* ta
     }
 }
 
-template <bool QUAL, int K, bool STATS, typename IT>
-__global__ __launch_bounds__(512, 4) void k_pileup(TileArgs A) {
+// LEAN: the register- and LDS-lean instance (process_chunk: the one-run window walk, every other
+// read alone in walk_complex) at five waves per SIMD instead of four; exact on any batch, ahead
+// while slow reads are few (launch_pileup_tiles routes).
+template <bool QUAL, int K, bool STATS, typename IT, bool LEAN = false>
+__global__ __launch_bounds__(512, LEAN ? 5 : 4) void k_pileup(TileArgs A) {
     extern __shared__ __attribute__((aligned(16))) unsigned char dyn[];
     __shared__ IT rng[8][2];  // per group: the tile's read range
     if (BC_ABL(A) & 64) return;
@@ -145,9 +148,11 @@ __global__ __launch_bounds__(512, 4) void k_pileup(TileArgs A) {
     const int S = A.S;
     const int g = wave / S, ws = wave - g * S;
     const int groups = nw / S;
+    constexpr int rec_bytes = LEAN ? kLeanRecBytes : kRecBytes;
+    constexpr int stage_region = LEAN ? kLeanStageRegion : kStageRegion;
     uint4* rec_all = (uint4*)dyn;
-    uint8_t* stage_all = dyn + (size_t)nw * kRecBytes;
-    uint32_t(*fin)[6][kTile] = (uint32_t(*)[6][kTile])(stage_all + (size_t)nw * kStageRegion);
+    uint8_t* stage_all = dyn + (size_t)nw * rec_bytes;
+    uint32_t(*fin)[6][kTile] = (uint32_t(*)[6][kTile])(stage_all + (size_t)nw * stage_region);
     double2* tab = (double2*)((uint8_t*)fin + (size_t)groups * kFinBytes);  // log2d::kTab for the tail
     // IT: the index type of reads, tiles and positions (int32_t when they fit: scalar math)
     const IT n_tiles = (IT)A.n_tiles;
@@ -232,8 +237,8 @@ __global__ __launch_bounds__(512, 4) void k_pileup(TileArgs A) {
             int pending = 0;
             typename WalkCounters<PLANES>::type W;
             counters_zero(W);
-            uint4* myrec = rec_all + wave * kTile * 3;
-            uint8_t* mystage = stage_all + (size_t)wave * kStageRegion + 16;
+            uint4* myrec = rec_all + wave * (rec_bytes / 16);
+            uint8_t* mystage = stage_all + (size_t)wave * stage_region + 16;
             auto chunk_nr = [&](IT b) { return b < hi ? (int)((hi - b) < 64 ? (hi - b) : 64) : 0; };
             IT base = lo + (IT)ws * 64;
             ReadFields F = load_fields(A, base, chunk_nr(base), lane);
@@ -242,8 +247,9 @@ __global__ __launch_bounds__(512, 4) void k_pileup(TileArgs A) {
 #endif
             for (; base < hi; base += (IT)S * 64) {
                 const IT nb = base + (IT)S * 64;
-                process_chunk<QUAL, K, PLANES>(A, base, chunk_nr(base), F, nb, chunk_nr(nb), lane, s8, gb, t0, P, edge,
-                                       beyond, bmask, myrec, mystage, qual_vec, W, cnt, acc, pending, bad);
+                process_chunk<QUAL, K, PLANES, LEAN>(A, base, chunk_nr(base), F, nb, chunk_nr(nb), lane, s8, gb, t0, P,
+                                                     edge, beyond, bmask, myrec, mystage, qual_vec, W, cnt, acc,
+                                                     pending, bad);
                 __builtin_amdgcn_wave_barrier();
 #ifdef BC_PHASE_TRACE
                 if (nch < 2) trace_stamp(A, 2 + nch);
@@ -581,7 +587,7 @@ struct TileShape {
     int64_t blocks;
     size_t lds;      // dynamic
 };
-TileShape tile_shape(int64_t n_tiles, int S) {
+TileShape tile_shape(int64_t n_tiles, int S, bool lean = false) {
     TileShape t;
     t.nw = S >= 4 ? S : 4;
     t.groups = t.nw / S;
@@ -589,8 +595,54 @@ TileShape tile_shape(int64_t n_tiles, int S) {
     const int64_t cap = 256 * 64;
     if (t.blocks > cap) t.blocks = cap;
     t.blocks = (t.blocks + 7) / 8 * 8;  // a multiple of the XCD count (see the kernel's tile mapping)
-    t.lds = pileup_lds_bytes(t.nw, t.groups);
+    t.lds = pileup_lds_bytes(t.nw, t.groups, lean);
     return t;
+}
+
+// ---- k_pileup's instances ----
+// The lean instance is built where it holds five waves per SIMD (at most 96 VGPRs, nothing
+// spilled: scripts/resources.py); every other combination has the
+// general instance alone.
+constexpr bool lean_built(bool qual, bool i32) { return !qual || i32; }
+typedef void (*TileKernel)(TileArgs);
+template <bool Q, int KK, bool ST, typename IT>
+TileKernel tile_kernel_of(bool lean) {
+    if constexpr (lean_built(Q, sizeof(IT) == 4)) {
+        if (lean) return k_pileup<Q, KK, ST, IT, true>;
+    }
+    return k_pileup<Q, KK, ST, IT, false>;
+}
+template <bool Q, int KK>
+TileKernel tile_kernel_qk(bool stats, bool i32, bool lean) {
+    if (stats) return i32 ? tile_kernel_of<Q, KK, true, int32_t>(lean) : tile_kernel_of<Q, KK, true, int64_t>(lean);
+    return i32 ? tile_kernel_of<Q, KK, false, int32_t>(lean) : tile_kernel_of<Q, KK, false, int64_t>(lean);
+}
+TileKernel tile_kernel(bool qual, int k, bool stats, bool i32, bool lean) {
+    if (qual) return k == 5 ? tile_kernel_qk<true, 5>(stats, i32, lean) : tile_kernel_qk<true, 6>(stats, i32, lean);
+    return k == 5 ? tile_kernel_qk<false, 5>(stats, i32, lean) : tile_kernel_qk<false, 6>(stats, i32, lean);
+}
+// > 64 KiB of dynamic LDS must be allowed per kernel (160 KiB per CU on gfx950), once
+void allow_lds(TileKernel fn) {
+    static TileKernel done[64];
+    static int n_done = 0;
+    for (int i = 0; i < n_done; ++i)
+        if (done[i] == fn) return;
+    (void)hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024);
+    if (n_done < 64) done[n_done++] = fn;
+}
+
+// Both instances are exact; the lean one is ahead while the reads walk_complex takes alone are
+// few.  A read of more than one run has at least three CIGAR ops (an op between the runs), so
+// such reads <= (CIGAR words - reads) / 2; a one-run read that begins or ends with a deletion is
+// slow with two ops and is not expected in numbers.  n_cigar_words counts the buffer: for a slice that shares a larger batch's CIGAR
+// buffer the bound is the larger batch's (never too small), and such a slice takes the general
+// instance unless every read of the buffer has one op (kLeanMaxSlowShare is zero: measured).
+bool tile_lean(const bc_reads& r, bool qual, bool i32, int instance) {
+    if (!lean_built(qual, i32) || instance == BC_INSTANCE_GENERAL) return false;
+    if (instance == BC_INSTANCE_LEAN) return true;
+    const int64_t extra = r.n_cigar_words - r.n_reads;
+    const double slow_max = extra > 0 ? (double)extra / 2.0 : 0.0;
+    return slow_max <= kLeanMaxSlowShare * (double)r.n_reads;
 }
 
 // the sparse sweep's: tiles per wave and workgroups of kSoloWaves waves (sump: whole quarter
@@ -664,10 +716,45 @@ void pileup_plan(const bc_reads& r, int64_t L, int shape, int tile_waves, bc_pla
     else (void)hipGetLastError();
 }
 
+void pileup_launch_info(const bc_reads& r, int64_t L, int shape, int tile_waves, int instance, uint32_t mbq, int k,
+                        bc_launch_info& o) {
+    o = bc_launch_info{};
+    o.blocks_per_cu = -1;
+    bc_plan p;
+    pileup_plan(r, L, shape, tile_waves, p);  // the kernel, and everything of the general instance
+    o.kernel = p.kernel;
+    o.waves_per_tile = p.waves_per_tile;
+    o.block_threads = p.block_threads;
+    o.lds_bytes = p.lds_bytes;
+    o.blocks = p.blocks;
+    if (p.kernel != BC_PLAN_TILES) {
+        o.blocks_per_cu = p.blocks_per_cu;  // (the sparse sweep's mbq = 0, k = 5 variant)
+        return;
+    }
+    const int64_t reach = r.max_end > L ? r.max_end : L;
+    const int64_t n_tiles = (reach + kTile - 1) / kTile;
+    const bool i32 = tiles_fit_i32(r.n_reads, n_tiles, r.max_span);
+    const bool lean = tile_lean(r, mbq > 0, i32, instance);
+    const TileShape t = tile_shape(n_tiles, p.waves_per_tile, lean);
+    o.lean = lean ? 1 : 0;
+    o.lds_bytes = (int32_t)(t.lds + 8 * 2 * (i32 ? 4 : 8));  // + rng, the static range hand-off
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        (void)hipGetLastError();
+        return;
+    }
+    const TileKernel fn = tile_kernel(mbq > 0, k, true, i32, lean);
+    allow_lds(fn);
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)fn, o.block_threads, t.lds) == hipSuccess)
+        o.blocks_per_cu = nb;
+    else (void)hipGetLastError();
+}
+
 hipError_t launch_pileup_tiles(hipStream_t s, const bc_reads& r, int64_t L, int64_t max_end, uint32_t mbq, int k,
                                bool stats, bool accumulate, double nf, double nf2, int32_t* counts, int32_t* cov,
                                double* pc, double* ent, double* sec, unsigned long long* d_err, int shape,
-                               int tile_waves, SumParts* parts) {
+                               int tile_waves, int instance, SumParts* parts) {
     PileArgs A = make_args(r, L, mbq);
     const int64_t reach = max_end > L ? max_end : L;  // edge tiles up to the furthest read end
     A.n_tiles = (reach + kTile - 1) / kTile;
@@ -734,7 +821,9 @@ hipError_t launch_pileup_tiles(hipStream_t s, const bc_reads& r, int64_t L, int6
 #undef BC_SOLO
         return hipGetLastError();
     }
-    const TileShape ts = tile_shape(A.n_tiles, S);
+    const bool i32 = tiles_fit_i32(A.n, A.n_tiles, A.max_span);
+    const bool lean = tile_lean(r, mbq > 0, i32, instance);
+    const TileShape ts = tile_shape(A.n_tiles, S, lean);
     const int nw = ts.nw;
     const int64_t blocks = ts.blocks;
     const dim3 grid((unsigned)blocks), block(64 * nw);
@@ -753,43 +842,17 @@ hipError_t launch_pileup_tiles(hipStream_t s, const bc_reads& r, int64_t L, int6
         if (!tbuf && hipMallocManaged((void**)&tbuf, 8 * (size_t)256 * 64 * 16 * kTracePhases) != hipSuccess) tbuf = nullptr;
         if (tn <= (size_t)256 * 64 * 16 * kTracePhases) A.trace = tbuf;
     }
-    const bool i32 = tiles_fit_i32(A.n, A.n_tiles, A.max_span);
     const TileArgs T = A;  // k_pileup takes the walk's fields only
-    // > 64 KiB of dynamic LDS must be allowed per kernel (160 KiB per CU on gfx950)
-#define BC_PILE(Q, KK, ST)                                                                                   \
-    do {                                                                                                     \
-        static bool attr_set = false;                                                                        \
-        if (!attr_set) {                                                                                     \
-            (void)hipFuncSetAttribute((const void*)k_pileup<Q, KK, ST, int32_t>,                             \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024);        \
-            (void)hipFuncSetAttribute((const void*)k_pileup<Q, KK, ST, int64_t>,                             \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024);        \
-            attr_set = true;                                                                                 \
-        }                                                                                                    \
-        if (i32) hipLaunchKernelGGL((k_pileup<Q, KK, ST, int32_t>), grid, block, lds, s, T);                 \
-        else hipLaunchKernelGGL((k_pileup<Q, KK, ST, int64_t>), grid, block, lds, s, T);                     \
-        if (A.trace && ++tcalls == 20) {                                                                     \
-            (void)hipStreamSynchronize(s);                                                                   \
-            if (FILE* f = std::fopen(tpath, "wb")) {                                                         \
-                std::fwrite(A.trace, 8, tn, f);                                                              \
-                std::fclose(f);                                                                              \
-            }                                                                                                \
-        }                                                                                                    \
-    } while (0)
-    if (mbq > 0) {
-        if (k == 5) {
-            if (stats) BC_PILE(true, 5, true); else BC_PILE(true, 5, false);
-        } else {
-            if (stats) BC_PILE(true, 6, true); else BC_PILE(true, 6, false);
-        }
-    } else {
-        if (k == 5) {
-            if (stats) BC_PILE(false, 5, true); else BC_PILE(false, 5, false);
-        } else {
-            if (stats) BC_PILE(false, 6, true); else BC_PILE(false, 6, false);
+    const TileKernel fn = tile_kernel(mbq > 0, k, stats, i32, lean);
+    allow_lds(fn);
+    hipLaunchKernelGGL(fn, grid, block, lds, s, T);
+    if (A.trace && ++tcalls == 20) {
+        (void)hipStreamSynchronize(s);
+        if (FILE* f = std::fopen(tpath, "wb")) {
+            std::fwrite(A.trace, 8, tn, f);
+            std::fclose(f);
         }
     }
-#undef BC_PILE
     return hipGetLastError();
 }
 

@@ -14,6 +14,9 @@ namespace bc {
 namespace {
 
 constexpr int kStage = 6144;     // LDS bytes per wave for a chunk's sequence (64 reads x <= 190 bp)
+// the lean instance's (k_pileup<.., LEAN>): 64 reads x 94 B, so that five four-wave workgroups fit
+// a CU's LDS (static_assert below)
+constexpr int kLeanStage = 6016;
 #include "bc_walk.h"
 
 constexpr int kTile = 64;
@@ -237,30 +240,55 @@ __device__ __forceinline__ void count_event(uint32_t e, uint32_t byte, uint32_t 
 // Complex chunks (a read with more than 8 CIGAR ops, more than 4 runs or huge indels): lanes own
 // positions, each read of the chunk is resolved at the lane's position by walking its CIGAR
 // from memory (records in LDS hold absolute sequence nibble indices), kBatch reads at a time.
-template <bool QUAL>
+//
+// LIST (the lean instance: the decision is per read): the reads walked are the nr set bits of
+// `list` (wave-uniform; bit l = read rbase + l of the chunk), and nothing of them is kept in
+// registers or LDS through the window walk: their four fields are read again, with scalar loads.
+template <bool QUAL, bool LIST = false>
 __device__ __forceinline__ void walk_complex(const TileArgs& A, const uint4* rec, int nr, int64_t P, int64_t t0,
                                              int64_t rbase, bool beyond, uint32_t mcn, uint32_t mcb,
-                                             unsigned long long& acc, int64_t& bad) {
+                                             unsigned long long& acc, int64_t& bad, unsigned long long list = 0) {
     const uint8_t* sp = A.seq ? A.seq : (const uint8_t*)A.pos;  // never dereferenced at a bad index
     for (int r0 = 0; r0 < nr; r0 += kBatch) {
         uint32_t e[kBatch];
+        int ri[kBatch];  // the reads' indices in the chunk
         for (int u = 0; u < kBatch; ++u) {
             const int r = r0 + u;
             uint32_t x = kNone;
+            int l = r;
             if (r < nr) {
-                const uint4 a = rec[r * 3];
-                x = resolve_slow((int)(P - (int64_t)(int32_t)a.x), (int)(t0 - (int32_t)a.x), rdl(mcn, r), a.y,
-                                 A.cigar + rdl(mcb, r));
+                if (LIST) {
+                    l = __builtin_ctzll(list);
+                    list &= list - 1;
+                    const int64_t i = rbase + l;
+                    const int32_t rp = A.pos[i];
+                    x = resolve_slow((int)(P - (int64_t)rp), (int)(t0 - rp), A.cig_n[i], A.seq_nib[i],
+                                     A.cigar + A.cig_beg[i]);
+                } else {
+                    const uint4 a = rec[r * 3];
+                    x = resolve_slow((int)(P - (int64_t)(int32_t)a.x), (int)(t0 - (int32_t)a.x), rdl(mcn, r), a.y,
+                                     A.cigar + rdl(mcb, r));
+                }
             }
 #pragma unroll
             for (int v = kBatch - 1; v > 0; --v) e[v] = e[v - 1];
             e[0] = x;
+            if (LIST) {
+#pragma unroll
+                for (int v = kBatch - 1; v > 0; --v) ri[v] = ri[v - 1];
+                ri[0] = l;
+            }
         }
 #pragma unroll
         for (int u = 0; u < kBatch / 2; ++u) {  // e[kBatch-1-u] holds read r0+u
             const uint32_t t = e[u];
             e[u] = e[kBatch - 1 - u];
             e[kBatch - 1 - u] = t;
+            if (LIST) {
+                const int tl = ri[u];
+                ri[u] = ri[kBatch - 1 - u];
+                ri[kBatch - 1 - u] = tl;
+            }
         }
         uint32_t byte[kBatch], qv[kBatch];
 #pragma unroll
@@ -271,7 +299,7 @@ __device__ __forceinline__ void walk_complex(const TileArgs& A, const uint4* rec
         }
 #pragma unroll
         for (int u = 0; u < kBatch; ++u)
-            count_event<QUAL>(e[u], byte[u], qv[u], A.mbq, beyond, rbase + r0 + u, acc, bad);
+            count_event<QUAL>(e[u], byte[u], qv[u], A.mbq, beyond, rbase + (LIST ? ri[u] : r0 + u), acc, bad);
     }
 }
 
@@ -280,16 +308,17 @@ __device__ __forceinline__ void walk_complex(const TileArgs& A, const uint4* rec
 // slot s): reads it*8 + s and it*8 + 8 + s in step it (two independent LDS chains in flight;
 // rounding the steps up to even only ever touches padding records).  NR: the chunk's largest
 // run count (1, 2, 4).  nr and it4 are wave-uniform.
-template <int NR, bool GAP, bool STAGED, bool QUAL, int NC>
+// STG: the stage's capacity in bytes, RS: the records' stride (bc_walk.h).
+template <int NR, bool GAP, bool STAGED, bool QUAL, int NC, int STG = kStage, int RS = 3>
 __device__ __forceinline__ void walk_swar(const TileArgs& A, const uint4* rec, const uint32_t* words, int nr, int gb,
                                           int s8, int64_t rbase, bool edge, uint32_t bmask, SwarCnt& C,
                                           uint32_t (&cnt)[6], int64_t& bad) {
-    const SeqSrc src{words, STAGED ? (int64_t)(kStage / 4) : A.seq_words, A.qual, A.qual_bytes, A.mbq};
+    const SeqSrc src{words, STAGED ? (int64_t)(STG / 4) : A.seq_words, A.qual, A.qual_bytes, A.mbq};
     const int iters = (((nr + 7) >> 3) + 1) & ~1;
     for (int it = 0; it < iters; it += 2) {
         const int r0 = it * 8 + s8, r1 = r0 + 8;
-        uint32_t x0 = window_events<NR, GAP, STAGED, QUAL>(src, rec, r0, gb);
-        uint32_t x1 = window_events<NR, GAP, STAGED, QUAL>(src, rec, r1, gb);
+        uint32_t x0 = window_events<NR, GAP, STAGED, QUAL, RS>(src, rec, r0, gb);
+        uint32_t x1 = window_events<NR, GAP, STAGED, QUAL, RS>(src, rec, r1, gb);
         if (edge) {  // events at positions >= L: the reference's out_of_range
             if ((x0 & bmask) && rbase + r0 < bad) bad = rbase + r0;
             if ((x1 & bmask) && rbase + r1 < bad) bad = rbase + r1;
@@ -305,17 +334,17 @@ __device__ __forceinline__ void walk_swar(const TileArgs& A, const uint4* rec, c
 // rounding the steps up to even only ever touches padding records).  NR: the chunk's largest
 // run count (1, 2, 4).  nr and the counters' fold counts are wave-uniform.  c32 = 32 * g: the lane's
 // window as a nibble-bit offset from the tile's first position.
-template <int NR, bool GAP, bool STAGED, int NC>
+template <int NR, bool GAP, bool STAGED, int NC, int STG = kStage, int RS = 3>
 __device__ __forceinline__ void walk_planes(const TileArgs& A, const uint4* rec, const uint32_t* words, int nr, int c32,
                                             int s8, int64_t rbase, bool edge, uint32_t bmask, Planes& W,
                                             uint32_t (&cnt)[6], int64_t& bad) {
-    const SeqSrc src{words, STAGED ? (int64_t)(kStage / 4) : A.seq_words, A.qual, A.qual_bytes, A.mbq};
+    const SeqSrc src{words, STAGED ? (int64_t)(STG / 4) : A.seq_words, A.qual, A.qual_bytes, A.mbq};
     const int iters = (((nr + 7) >> 3) + 1) & ~1;
 #pragma unroll 1
     for (int it = 0; it < iters; it += 2) {
         const int r0 = it * 8 + s8, r1 = r0 + 8;
-        uint32_t x0 = tile_events<NR, GAP, STAGED>(src, rec, r0, c32);
-        uint32_t x1 = tile_events<NR, GAP, STAGED>(src, rec, r1, c32);
+        uint32_t x0 = tile_events<NR, GAP, STAGED, RS>(src, rec, r0, c32);
+        uint32_t x1 = tile_events<NR, GAP, STAGED, RS>(src, rec, r1, c32);
         if (edge) {  // events at positions >= L: the reference's out_of_range
             if ((x0 & bmask) && rbase + r0 < bad) bad = rbase + r0;
             if ((x1 & bmask) && rbase + r1 < bad) bad = rbase + r1;
@@ -327,19 +356,19 @@ __device__ __forceinline__ void walk_planes(const TileArgs& A, const uint4* rec,
 }
 
 // the walk of the counters' kind (overloads)
-template <int NR, bool GAP, bool STAGED, bool QUAL, int NC>
+template <int NR, bool GAP, bool STAGED, bool QUAL, int NC, int STG = kStage, int RS = 3>
 __device__ __forceinline__ void walk_counters(const TileArgs& A, const uint4* rec, const uint32_t* words, int nr,
                                               int /* gb: the SWAR walk's */, int s8, int64_t rbase, bool edge,
                                               uint32_t bmask, Planes& W, uint32_t (&cnt)[6], int64_t& bad) {
     static_assert(!QUAL, "the planes walk applies no quality mask");
     const int c32 = (int)(threadIdx.x & 56u) * 4;  // 32 * (lane >> 3)
-    walk_planes<NR, GAP, STAGED, NC>(A, rec, words, nr, c32, s8, rbase, edge, bmask, W, cnt, bad);
+    walk_planes<NR, GAP, STAGED, NC, STG, RS>(A, rec, words, nr, c32, s8, rbase, edge, bmask, W, cnt, bad);
 }
-template <int NR, bool GAP, bool STAGED, bool QUAL, int NC>
+template <int NR, bool GAP, bool STAGED, bool QUAL, int NC, int STG = kStage, int RS = 3>
 __device__ __forceinline__ void walk_counters(const TileArgs& A, const uint4* rec, const uint32_t* words, int nr, int gb,
                                               int s8, int64_t rbase, bool edge, uint32_t bmask, SwarCnt& C,
                                               uint32_t (&cnt)[6], int64_t& bad) {
-    walk_swar<NR, GAP, STAGED, QUAL, NC>(A, rec, words, nr, gb, s8, rbase, edge, bmask, C, cnt, bad);
+    walk_swar<NR, GAP, STAGED, QUAL, NC, STG, RS>(A, rec, words, nr, gb, s8, rbase, edge, bmask, C, cnt, bad);
 }
 
 constexpr int kFinBytes = 6 * kTile * 4;  // a group's reduced counts
@@ -356,8 +385,17 @@ static_assert(2 * (8 * (kRecBytes + kStageRegion) + kFinBytes + kLog2TabBytes) <
 static_assert(4 * ((4 * (kRecBytes + kStageRegion) + kFinBytes + kLog2TabBytes + 64 + kLdsGranule - 1) / kLdsGranule *
                    kLdsGranule) <= 160 * 1024,
               "4 four-wave blocks per CU");
-__host__ __device__ inline size_t pileup_lds_bytes(int nw, int groups) {
-    return (size_t)nw * (kRecBytes + kStageRegion) + (size_t)groups * kFinBytes + kLog2TabBytes;
+// The lean instance (k_pileup<.., LEAN = true>: one-run, ungapped reads in the window walk, every
+// other read alone in walk_complex): one uint4 record per read and kLeanStage bytes of stage, so
+// that FIVE four-wave blocks of one tile fit (5 x 32,000 B after rounding).
+constexpr int kLeanRecBytes = kTile * 16;
+constexpr int kLeanStageRegion = kLeanStage + 32;
+static_assert(5 * ((4 * (kLeanRecBytes + kLeanStageRegion) + kFinBytes + kLog2TabBytes + 64 + kLdsGranule - 1) /
+                   kLdsGranule * kLdsGranule) <= 160 * 1024,
+              "5 lean four-wave blocks per CU");
+__host__ __device__ inline size_t pileup_lds_bytes(int nw, int groups, bool lean = false) {
+    return (size_t)nw * (lean ? kLeanRecBytes + kLeanStageRegion : kRecBytes + kStageRegion) +
+           (size_t)groups * kFinBytes + kLog2TabBytes;
 }
 
 // Per-read fields of a chunk (lane = read), loaded one chunk ahead of their use.
@@ -422,13 +460,23 @@ constexpr uint32_t kSpecSlack = 128;  // bytes staged beyond the last read's fir
 // batch usually lie in file order: [first read's seq, last read's seq + slack)) by LDS-DMA,
 // issued together with the CIGAR loads, so a chunk costs one memory round trip before its walk;
 // the exact segment, known after the decode, is restaged only when it is not covered.
-template <bool QUAL, int K, bool PLANES>
+//
+// LEAN (k_pileup's lean instance): only the staged, one-run, ungapped window walk and walk_complex
+// are instantiated, and the choice between them is made per READ.  A read that decodes to more
+// than one run, has a deletion / ref-skip or is complex is *slow*: its record is empty (no events
+// in the window walk) and it is walked alone, after the window walk, by walk_complex over the
+// ballot of the chunk's slow reads.  A chunk whose fast reads' segment does not fit the stage
+// after the exact restage is walked by walk_complex as a whole.  The counts and the first
+// offending read (a minimum over read indices) are those of the general instance.
+template <bool QUAL, int K, bool PLANES, bool LEAN = false>
 __device__ __forceinline__ void process_chunk(const TileArgs& A, int64_t base, int nr, ReadFields& F,
                                               int64_t next_base, int next_nr, int lane, int s8, int gb, int64_t t0,
                                               int64_t P, bool edge, bool beyond, uint32_t bmask, uint4* myrec,
                                               uint8_t* mystage, bool qual_vec, typename WalkCounters<PLANES>::type& W,
                                               uint32_t (&cnt)[6],
                                               unsigned long long& acc, int& pending, int64_t& bad) {
+    constexpr int STG = LEAN ? kLeanStage : kStage;  // the stage's capacity
+    constexpr int RS = LEAN ? 1 : 3;                 // uint4 per record
     // ---- chunk load: CIGAR -> run table (VALU), speculative staging in flight meanwhile
     RunTable T;
     const uint32_t mpos = F.pos, mcb = F.cb, mcn = F.cn, msn = F.sn;
@@ -455,16 +503,18 @@ __device__ __forceinline__ void process_chunk(const TileArgs& A, int64_t base, i
         spec_lo = (rdl(msn, 0) >> 1) & ~15u;
         spec_hi = (rdl(msn, nr - 1) >> 1) + kSpecSlack;
         spec_hi = spec_hi < buf_end ? spec_hi : buf_end;
-        spec = spec_hi > spec_lo && spec_hi - spec_lo <= (uint32_t)kStage;
+        spec = spec_hi > spec_lo && spec_hi - spec_lo <= (uint32_t)STG;
         if (spec) stage_dma<64>(mystage, A.seq + spec_lo, spec_hi - spec_lo, lane);
     }
-    if (lane < nr) T = decode_runs(w, mcn, cmax);
-    const bool cx = __any(T.complex);
-    const bool gap = __any(T.gap);
-    const int maxrun = (int)wave_reduce<true>((uint32_t)T.nrun);
-    // ---- the chunk's exact sequence segment (BC_SEQ_EVENT bytes)
+    if (lane < nr) T = LEAN ? decode_runs<1>(w, mcn, cmax) : decode_runs(w, mcn, cmax);
+    // LEAN: no chunk-wide property is reduced; `slow` is the lane's own read
+    const bool slow = LEAN && (T.complex || T.gap || T.nrun > 1);
+    const bool cx = LEAN ? false : __any(T.complex);
+    const bool gap = LEAN ? false : __any(T.gap);
+    const int maxrun = LEAN ? 1 : (int)wave_reduce<true>((uint32_t)T.nrun);
+    // ---- the chunk's exact sequence segment (BC_SEQ_EVENT bytes; LEAN: of its fast reads)
     uint32_t blo = 0xFFFFFFFFu, bhi = 0;
-    if (lane < nr && T.qlen) {
+    if (lane < nr && T.qlen && !slow) {
         blo = msn >> 1;
         bhi = (msn + T.qlen + 1) >> 1;
     }
@@ -473,14 +523,29 @@ __device__ __forceinline__ void process_chunk(const TileArgs& A, int64_t base, i
     seg_lo = seg_hi > seg_lo ? (seg_lo & ~15u) : 0u;
     const bool spec_ok = spec && !cx && (seg_hi <= seg_lo || (seg_lo >= spec_lo && seg_hi <= spec_hi));
     if (spec_ok) seg_lo = spec_lo;  // the stage holds [spec_lo, spec_hi)
-    const bool staged = !cx && (spec_ok || seg_hi - seg_lo <= (uint32_t)kStage) && !(BC_ABL(A) & 32);
+    const bool staged = !cx && (spec_ok || seg_hi - seg_lo <= (uint32_t)STG) && !(BC_ABL(A) & 32);
+    // LEAN: the reads walk_complex takes (wave-uniform; all of them when nothing is staged)
+    const unsigned long long slow_list = LEAN ? __ballot(lane < nr && (slow || !staged)) : 0ull;
     if (spec && !spec_ok) stage_wait();  // the speculative copy must land before it is overwritten
     if (staged && !spec_ok) {
         if (dma) stage_dma<64>(mystage, A.seq + seg_lo, seg_hi - seg_lo, lane);
         else stage_regs<QUAL>(A, mystage, seg_lo, seg_hi, lane, qual_vec);
     }
     const uint32_t qbase = staged ? 2u * seg_lo : 0u;
-    if (cx) {  // walk_complex reads {pos, absolute seq_nib}
+    if (LEAN) {
+        // one uint4 per read: run 0 of a fast read (the layouts below at NR = 1), nothing of a slow
+        // one (an empty range in either layout)
+        const uint32_t rel = mpos - (uint32_t)t0, rel4 = rel * 4u;
+        uint32_t nb0 = msn - qbase + (uint32_t)T.qd[0];
+        uint4 v = make_uint4(0u, 0u, 0u, 0u);
+        if (PLANES) {
+            nb0 = (nb0 - rel) * 4u;
+            if (!slow) v = make_uint4(rel4 + T.st[0] * 4u, rel4 + T.en[0] * 4u, nb0, 0u);
+        } else if (!slow) {
+            v = make_uint4(mpos, T.span * 4u, pack_rr(T.st[0], T.en[0]), nb0);
+        }
+        myrec[lane] = v;
+    } else if (cx) {  // walk_complex reads {pos, absolute seq_nib}
         myrec[lane * 3] = make_uint4(mpos, msn, 0u, 0u);
     } else if (!PLANES) {  // read-relative records (window_events)
         uint32_t rr[kMaxRuns], nb[kMaxRuns];
@@ -522,6 +587,21 @@ __device__ __forceinline__ void process_chunk(const TileArgs& A, int64_t base, i
     __builtin_amdgcn_wave_barrier();
     const int64_t rbase = base;
     if (BC_ABL(A) & 4) {
+    } else if (LEAN) {
+        if (staged) {
+            walk_counters<1, false, true, QUAL, K, STG, RS>(A, myrec, (const uint32_t*)mystage, nr, gb, s8, rbase, edge,
+                                                            bmask, W, cnt, bad);
+            counters_reserve<K>(W, cnt, s8);  // room for the next chunk
+        }
+        if (slow_list) {
+            const int ns = __popcll(slow_list);
+            if (pending + ns >= (1 << kField) - 1) {
+                flush_acc(acc, cnt);
+                pending = 0;
+            }
+            pending += ns;
+            walk_complex<QUAL, true>(A, myrec, ns, P, t0, rbase, edge && beyond, 0u, 0u, acc, bad, slow_list);
+        }
     } else if (cx) {
         if (pending + nr >= (1 << kField) - 1) {
             flush_acc(acc, cnt);

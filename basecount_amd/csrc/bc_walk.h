@@ -317,7 +317,8 @@ __device__ __forceinline__ uint32_t qual_mask_at(const SeqSrc& S, int64_t n0) {
     return m;
 }
 
-// Walk record of a read (3 x uint4 in LDS, written at chunk load):
+// Walk record of a read (3 x uint4 in LDS, written at chunk load; RS: the records' stride in
+// uint4, 1 for the lean instance, whose reads have one run and whose records are [0] alone):
 //   [0] = {pos, 4*span, rr0, nb0}  [1] = {rr1, nb1, rr2, nb2}  [2] = {rr3, nb3, 0, 0}
 // M run k: rr = 4*st | 4*en << 16 (empty: st == en), nb = nibble index (staged: relative to the
 // stage) of the base at reference offset 0, i.e. seq_nib + qd.
@@ -335,13 +336,14 @@ __device__ __forceinline__ uint32_t range_mask(int lo4, int hi4, int j4) {
 
 // The 8 event classes (x) one read has in the lane's window [gb, gb + 8): its M runs' bases
 // (one funnel-shifted fetch each) and, GAP, class 1100 on the rest of [0, span).
-template <int NR, bool GAP, bool STAGED, bool QUAL>
+template <int NR, bool GAP, bool STAGED, bool QUAL, int RS = 3>
 __device__ __forceinline__ uint32_t window_events(const SeqSrc& S, const uint4* rec, int r, int gb) {
-    const uint4 a = rec[r * 3];
+    static_assert(RS == 3 || NR == 1, "one-uint4 records hold one run");
+    const uint4 a = rec[r * RS];
     uint4 b = make_uint4(0u, 0u, 0u, 0u);
     uint2 c = make_uint2(0u, 0u);
-    if (NR > 1) b = rec[r * 3 + 1];
-    if (NR > 3) c = *(const uint2*)&rec[r * 3 + 2];
+    if (NR > 1) b = rec[r * RS + 1];
+    if (NR > 3) c = *(const uint2*)&rec[r * RS + 2];
     const int j0 = gb - (int)a.x;  // window start relative to the read start
     const int j4 = j0 * 4;
     const uint32_t rr[4] = {a.z, b.x, b.z, c.x};
@@ -401,9 +403,10 @@ __device__ __forceinline__ uint32_t tile_fetch(const SeqSrc& S, uint32_t nb, int
 
 // The 8 event classes (x) read r has in the lane's window: its M runs' bases (one funnel-shifted
 // fetch each) and, GAP, class 1100 on the rest of its range.
-template <int NR, bool GAP, bool STAGED>
+template <int NR, bool GAP, bool STAGED, int RS = 3>
 __device__ __forceinline__ uint32_t tile_events(const SeqSrc& S, const uint4* rec, int r, int c32) {
-    const uint4 a = rec[r * 3];
+    static_assert(RS == 3 || NR == 1, "one-uint4 records hold one run");
+    const uint4 a = rec[r * RS];
     if (NR == 1) {
         const uint32_t m = tile_mask((int)a.x, (int)a.y, c32);
         uint32_t x = tile_fetch<STAGED>(S, a.z, c32) & m;

@@ -193,6 +193,19 @@ class BcPlan(C.Structure):
 
 
 PLAN_KERNELS = ("rc", "solo", "tiles")  # BC_PLAN_*
+INSTANCES = {"auto": 0, "general": 1, "lean": 2}  # BC_INSTANCE_*
+
+
+class BcLaunchInfo(C.Structure):
+    _fields_ = [
+        ("kernel", C.c_int32),
+        ("lean", C.c_int32),
+        ("waves_per_tile", C.c_int32),
+        ("block_threads", C.c_int32),
+        ("lds_bytes", C.c_int32),
+        ("blocks_per_cu", C.c_int32),  # -1: no device to ask
+        ("blocks", C.c_int64),
+    ]
 
 
 class BcError(RuntimeError):
@@ -219,6 +232,9 @@ def lib() -> C.CDLL:
         "bc_sync": ([vp], C.c_int),
         "bc_ctx_set_shape": ([vp, C.c_int, C.c_int, C.c_int], C.c_int),
         "bc_pileup_plan": ([C.POINTER(BcReads), i64, C.c_int, C.c_int, C.POINTER(BcPlan)], C.c_int),
+        "bc_ctx_set_instance": ([vp, C.c_int], C.c_int),
+        "bc_pileup_launch_info": ([C.POINTER(BcReads), i64, C.c_int, C.c_int, C.c_int, u32, C.c_int,
+                                   C.POINTER(BcLaunchInfo)], C.c_int),
         "bc_malloc": ([vp, C.c_size_t, C.POINTER(vp)], C.c_int),
         "bc_free": ([vp, vp], C.c_int),
         "bc_memcpy_h2d": ([vp, vp, vp, C.c_size_t], C.c_int),
@@ -338,6 +354,27 @@ def pileup_plan(reads, L: int, shape: str = "auto", tile_waves: int = 0) -> dict
     return {"kernel": PLAN_KERNELS[p.kernel], "waves_per_tile": p.waves_per_tile, "block_threads": p.block_threads,
             "lds_bytes": p.lds_bytes, "blocks": p.blocks, "blocks_per_cu": p.blocks_per_cu,
             "tiles_per_wave": p.tiles_per_wave, "reads_per_tile": p.reads_per_tile}
+
+
+def pileup_launch_info(reads, L: int, shape: str = "auto", tile_waves: int = 0, instance: str = "auto",
+                       mbq: int = 0, k: int = 5) -> dict:
+    """bc_pileup_launch_info: the instance a bc_pileup call launches on a context set to (shape,
+    tile_waves, instance).  ``reads`` as for pileup_plan; a dict may also give n_cigar_words (the
+    routing bound's input; default: one op per read).  Returns kernel, lean (bool), waves_per_tile,
+    block_threads, lds_bytes, blocks and blocks_per_cu of that very kernel (-1 without a device)."""
+    if isinstance(reads, dict):
+        r = BcReads()
+        r.n_reads, r.max_span, r.max_end = int(reads["n_reads"]), int(reads["max_span"]), int(reads["max_end"])
+        r.n_cigar_words = int(reads.get("n_cigar_words", r.n_reads))
+        r.sorted, r.seq_layout = 1, BC_SEQ_EVENT
+    else:
+        r = reads.r if isinstance(reads, DeviceReads) else reads
+    p = BcLaunchInfo()
+    check(lib().bc_pileup_launch_info(C.byref(r), int(L), SHAPES[shape], int(tile_waves), INSTANCES[instance], int(mbq),
+                                      int(k), C.byref(p)))
+    return {"kernel": PLAN_KERNELS[p.kernel], "lean": bool(p.lean), "waves_per_tile": p.waves_per_tile,
+            "block_threads": p.block_threads, "lds_bytes": p.lds_bytes, "blocks": p.blocks,
+            "blocks_per_cu": p.blocks_per_cu}
 
 
 class DeviceBuffer:
@@ -461,6 +498,12 @@ class Context:
         reads_per_block 0 or 1..32768.  ``shape_args`` keeps the arguments in force."""
         check(lib().bc_ctx_set_shape(self.h, SHAPES[shape], int(tile_waves), int(reads_per_block)))
         self.shape_args = (shape, int(tile_waves), int(reads_per_block))
+
+    def set_instance(self, instance: str = "auto") -> None:
+        """The tiled k_pileup's instance (bc_ctx_set_instance): "auto" (lean while the batch's
+        bound on multi-run reads is small), "general" or "lean" (A/B runs and tests; both are
+        exact on every batch)."""
+        check(lib().bc_ctx_set_instance(self.h, INSTANCES[instance]))
 
     def sync(self):
         check(lib().bc_sync(self.h))

@@ -196,6 +196,46 @@ typedef struct bc_plan {
     double reads_per_tile;
 } bc_plan;
 int bc_pileup_plan(const bc_reads* reads, int64_t ref_len, int shape, int tile_waves, bc_plan* out);
+
+/* The tiled k_pileup has two instances, both exact on every batch:
+ *   general  the one bc_pileup_plan describes (run tables of up to four runs, deletions, unstaged
+ *            chunks; four four-wave workgroups per CU);
+ *   lean     only the one-run, ungapped window walk, with every other read (an indel, a skip,
+ *            more than 8 ops) walked alone per position; fewer registers and less LDS, so FIVE
+ *            four-wave workgroups per CU.  10 % ahead on a batch without such reads, behind
+ *            from one such read in 64 on.
+ * BC_INSTANCE_AUTO therefore takes the lean instance only when (n_cigar_words - n_reads) / 2, an
+ * upper bound of the reads with more than one run, is zero (every read has ONE CIGAR op: an
+ * ungapped, unclipped batch), and where a lean instance is built (no quality threshold, or 32-bit
+ * indices).  n_cigar_words is the CIGAR buffer's count: a bc_reads that is a slice of a larger
+ * batch and shares its buffer is judged by the larger batch's count, never by another slice's
+ * alone, and keeps the general instance unless every read of the buffer has one op (the bound
+ * can be too large for a slice, never too small).  bc_ctx_set_instance forces one for A/B runs and tests
+ * (BC_INSTANCE_LEAN where none is built keeps the general one).
+ * bc_pileup_plan keeps describing the GENERAL tiled instance whatever bc_pileup launches;
+ * bc_pileup_launch_info reports the instance a bc_pileup(ctx, reads, ref_len, mbq, k, ...) call
+ * launches on a context set to (shape, tile_waves, instance); like bc_pileup_plan it needs no
+ * context, reads no pointer of reads and enqueues nothing:
+ *   kernel, waves_per_tile, block_threads, blocks   as in bc_plan
+ *   lean           1 the lean instance, 0 the general one (0 for the other kernels)
+ *   lds_bytes      LDS per workgroup, dynamic + static, of that instance
+ *   blocks_per_cu  hipOccupancyMaxActiveBlocksPerMultiprocessor's answer for that very kernel
+ *                  (mbq, k and the index width included); -1 when no device is visible          */
+#define BC_INSTANCE_AUTO 0
+#define BC_INSTANCE_GENERAL 1
+#define BC_INSTANCE_LEAN 2
+int bc_ctx_set_instance(bc_ctx* ctx, int instance);
+typedef struct bc_launch_info {
+    int32_t kernel;
+    int32_t lean;
+    int32_t waves_per_tile;
+    int32_t block_threads;
+    int32_t lds_bytes;
+    int32_t blocks_per_cu;
+    int64_t blocks;
+} bc_launch_info;
+int bc_pileup_launch_info(const bc_reads* reads, int64_t ref_len, int shape, int tile_waves, int instance,
+                          uint32_t min_base_quality, int k, bc_launch_info* out);
 int bc_sync(bc_ctx* ctx);
 
 /* Library-owned device memory helpers (for hosts without another allocator). */
