@@ -10,6 +10,7 @@
 #include <thread>
 #include <vector>
 
+#include "bc_cohort.h"
 #include "bc_internal.h"
 
 namespace {
@@ -1236,6 +1237,43 @@ int bc_pileup_segments(bc_ctx* c, const bc_reads* r, int n_seg, const int64_t* d
     if (rc != BC_OK || !d_sum) return rc;
     Timed tm(c, BC_K_SUMMARY);
     HIP_TRY(bc::launch_sum_segments(c->stream, n_seg, d_ref_len, d_voff, d_cov, d_ent, d_sum));
+    return BC_OK;
+}
+
+int bc_segments_rebase(bc_ctx* c, int64_t n_reads, int n_seg, const int64_t* d_read_beg, const uint64_t* d_cig_base,
+                       const uint64_t* d_nib_base, uint64_t cig_words_total, uint64_t nib_total,
+                       const uint32_t* d_cig_beg, const uint32_t* d_seq_nib, uint32_t* d_cig_beg_out,
+                       uint32_t* d_seq_nib_out) {
+    if (!c) return fail(BC_E_ARG, "bc_segments_rebase: ctx is NULL");
+    if (n_reads < 0 || n_reads > 0x7FFFFFFFll) return fail(BC_E_ARG, "bc_segments_rebase: n_reads must lie in [0, 2^31)");
+    if (n_seg < 1) return fail(BC_E_ARG, "bc_segments_rebase: n_seg must be > 0");
+    if (!bcc_fits(cig_words_total, nib_total))
+        return fail(BC_E_ARG, "bc_segments_rebase: the shared buffers must hold fewer than 2^32 CIGAR words and nibbles");
+    if (!d_read_beg || !d_cig_base || !d_nib_base) return fail(BC_E_ARG, "bc_segments_rebase: NULL segment table");
+    if (n_reads > 0 && (!d_cig_beg || !d_seq_nib || !d_cig_beg_out || !d_seq_nib_out))
+        return fail(BC_E_ARG, "bc_segments_rebase: NULL per-read array");
+    DeviceGuard g(c->device);
+    Timed tm(c, BC_K_INDEX);
+    HIP_TRY(bc::launch_seg_rebase(c->stream, n_reads, d_read_beg, n_seg, d_cig_base, d_nib_base, d_cig_beg, d_seq_nib,
+                                  d_cig_beg_out, d_seq_nib_out));
+    return BC_OK;
+}
+
+int bc_amplicons_segments(bc_ctx* c, const int32_t* d_cov, const double* d_ent, const double* d_sec, int n_seg,
+                          const int64_t* d_ref_len, const int64_t* d_voff, const int64_t* d_lo, const int64_t* d_hi,
+                          int32_t n_tiles, double* d_out) {
+    if (!c) return fail(BC_E_ARG, "bc_amplicons_segments: ctx is NULL");
+    if (n_seg < 1) return fail(BC_E_ARG, "bc_amplicons_segments: n_seg must be > 0");
+    if (n_tiles < 0) return fail(BC_E_ARG, "bc_amplicons_segments: n_tiles < 0");
+    if ((int64_t)n_seg * n_tiles > 0x7FFFFFFFll)
+        return fail(BC_E_ARG, "bc_amplicons_segments: n_seg * n_tiles must stay below 2^31");
+    if (n_tiles == 0) return BC_OK;
+    if (!d_cov || !d_ent || !d_sec || !d_ref_len || !d_voff || !d_lo || !d_hi || !d_out)
+        return fail(BC_E_ARG, "bc_amplicons_segments: NULL argument");
+    DeviceGuard g(c->device);
+    Timed tm(c, BC_K_AMPLICONS);
+    HIP_TRY(bc::launch_amplicons_segments(c->stream, d_cov, d_ent, d_sec, n_seg, d_ref_len, d_voff, d_lo, d_hi,
+                                          n_tiles, d_out));
     return BC_OK;
 }
 

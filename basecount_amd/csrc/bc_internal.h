@@ -206,7 +206,16 @@ hipError_t launch_seg_vpos(hipStream_t s, const int32_t* pos, int64_t n, const i
 // bc_summary's 4 doubles of every segment's slice [voff[i], voff[i] + ref_len[i]) into out[i][4]
 hipError_t launch_sum_segments(hipStream_t s, int n_seg, const int64_t* ref_len, const int64_t* voff,
                                const int32_t* cov, const double* ent, double* out);
-
+// ---- a cohort's files as segments (bc_cohort.h: bc_segments_rebase, bc_amplicons_segments) ----
+// out_cig[i] = in_cig[i] + cig_base[segment of read i], out_nib[i] = in_nib[i] + nib_base[segment]
+// (uint32; in place when in == out)
+hipError_t launch_seg_rebase(hipStream_t s, int64_t n, const int64_t* read_beg, int n_seg, const uint64_t* cig_base,
+                             const uint64_t* nib_base, const uint32_t* in_cig, const uint32_t* in_nib,
+                             uint32_t* out_cig, uint32_t* out_nib);
+// bc_amplicons' 6 doubles of window t clipped to segment seg's slice into out[seg][t][6]
+hipError_t launch_amplicons_segments(hipStream_t s, const int32_t* cov, const double* ent, const double* sec,
+                                     int n_seg, const int64_t* ref_len, const int64_t* voff, const int64_t* lo,
+                                     const int64_t* hi, int n_tiles, double* out);
 
 // ---- BGZF inflate (bc_inflate.hip): one wave per block, every descriptor checked on the device ----
 hipError_t launch_inflate(hipStream_t s, const uint8_t* comp, uint64_t comp_bytes, const bc_zblock* blocks, int64_t n,

@@ -10,6 +10,7 @@
 // the LDS atomic rate; see DESIGN.md for the roofline accounting.
 #include <cstring>
 
+#include "bc_cohort.h"
 #include "bc_internal.h"
 #include "bc_log2.h"
 #include "bc_npsum.h"
@@ -989,32 +990,31 @@ __device__ __forceinline__ unsigned long long wave_kth(const unsigned long long 
 }
 constexpr int kAmpSortE = 8;  // windows of <= 512 positions: medians by one wave's bitonic sort
 
-__global__ __launch_bounds__(256) void k_amplicon(const int32_t* cov, const double* ent, const double* sec, int64_t L,
-                                                  const int64_t* lo_a, const int64_t* hi_a, double* out) {
+static_assert(64 * kAmpSortE == BCC_SORT_MAX, "bc_cohort.h names the sorted windows' size");
+
+// One window by one 256-thread workgroup: positions [w.lo, w.lo + w.n) of the three arrays (the
+// window clipped by bcc_clip to the reference, or to the segment, the arrays belong to) into o[6].
+__device__ __forceinline__ void amplicon_window(const int32_t* cov, const double* ent, const double* sec,
+                                                const bcc_window w, double* o) {
     __shared__ unsigned s_hist[256];
     __shared__ unsigned long long s_sel[2];
     __shared__ long long s_red[4];
     __shared__ int s_off[(2 << kLv) - 1], s_len[(2 << kLv) - 1];
     __shared__ double s_val[2 << kLv];
-    const int t = blockIdx.x;
-    int64_t lo = lo_a[t], hi = hi_a[t];
-    if (lo < 0) lo = 0;
-    if (hi > L - 1) hi = L - 1;
-    double* o = out + (int64_t)t * 6;
-    if (lo > hi) {
+    if (bcc_empty(w)) {  // (uniform)
         if (threadIdx.x == 0)
             for (int j = 0; j < 6; ++j) o[j] = -1.0;
         return;
     }
-    const int64_t n = hi - lo + 1;
-    const int64_t k1 = (n - 1) / 2, k2 = n / 2;
+    const int64_t lo = w.lo, n = w.n;
+    const int64_t k1 = bcc_k1(n), k2 = bcc_k2(n);
     __shared__ unsigned long long s_med[3][2];
     constexpr int kWin = 64 * kAmpSortE;
     // windows of amplicon size (C4: ~300 positions): the three arrays staged in LDS once (every
     // load issued at once), then the sorts, the sums and numpy's pairwise means read LDS only
     __shared__ int32_t s_c[kWin];
     __shared__ double s_e[kWin], s_s[kWin];
-    const bool sorted = n <= kWin;  // (uniform)
+    const bool sorted = bcc_sorted_path(n);  // (uniform)
     if (sorted) {
         for (int i = threadIdx.x; i < n; i += blockDim.x) {
             s_c[i] = cov[lo + i];
@@ -1074,6 +1074,23 @@ __global__ __launch_bounds__(256) void k_amplicon(const int32_t* cov, const doub
         o[4] = means[1];
         o[5] = meds[1];
     }
+}
+
+__global__ __launch_bounds__(256) void k_amplicon(const int32_t* cov, const double* ent, const double* sec, int64_t L,
+                                                  const int64_t* lo_a, const int64_t* hi_a, double* out) {
+    const int t = blockIdx.x;
+    amplicon_window(cov, ent, sec, bcc_clip(lo_a[t], hi_a[t], L), out + (int64_t)t * 6);
+}
+
+// The same windows on every segment of a virtual reference (bc_amplicons_segments): workgroup
+// seg * n_tiles + t takes window t of segment seg, clipped to the segment's own [0, ref_len - 1] and
+// read from its slice at voff[seg]: a pad or a neighbouring segment is never touched.
+__global__ __launch_bounds__(256) void k_amplicon_segments(const int32_t* cov, const double* ent, const double* sec,
+                                                           const int64_t* ref_len, const int64_t* voff, int n_tiles,
+                                                           const int64_t* lo_a, const int64_t* hi_a, double* out) {
+    const int seg = blockIdx.x / n_tiles, t = blockIdx.x - seg * n_tiles;
+    const int64_t v = voff[seg];
+    amplicon_window(cov + v, ent + v, sec + v, bcc_clip(lo_a[t], hi_a[t], ref_len[seg]), out + (int64_t)blockIdx.x * 6);
 }
 
 // ---- the fused --summarise-with-bed tail (main.py:469-551) after kernel 1 + 2 -------------------
@@ -1493,6 +1510,15 @@ hipError_t launch_amplicons(hipStream_t s, const int32_t* cov, const double* ent
                             const int64_t* lo, const int64_t* hi, int n_tiles, double* out) {
     if (n_tiles <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_amplicon, dim3((unsigned)n_tiles), dim3(256), 0, s, cov, ent, sec, L, lo, hi, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_amplicons_segments(hipStream_t s, const int32_t* cov, const double* ent, const double* sec,
+                                     int n_seg, const int64_t* ref_len, const int64_t* voff, const int64_t* lo,
+                                     const int64_t* hi, int n_tiles, double* out) {
+    if (n_seg <= 0 || n_tiles <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_amplicon_segments, dim3((unsigned)((int64_t)n_seg * n_tiles)), dim3(256), 0, s, cov, ent,
+                       sec, ref_len, voff, n_tiles, lo, hi, out);
     return hipGetLastError();
 }
 

@@ -8,6 +8,7 @@
 //   k_seg_vpos      one lane per read: its segment (a search of read_beg[]), vpos = voff + pos;
 //   k_sum_segments  one workgroup per segment: bc_summary's four doubles over the segment's slice
 //                   of the coverage and entropy, by the numpy-exact routines of bc_npsum.h.
+#include "bc_cohort.h"
 #include "bc_internal.h"
 #include "bc_npsum.h"
 
@@ -104,7 +105,39 @@ __global__ __launch_bounds__(256) void k_sum_segments(const int64_t* __restrict_
     }
 }
 
+// A cohort batch (bc_cohort.h): read i indexes the arrays of the file its segment belongs to; in
+// the shared buffers its CIGAR words and its nibbles lie one base further on.  k_seg_vpos's
+// schedule: a wave inside one segment searches twice with uniform addresses, a wave that straddles
+// segments once per lane.  No CIGAR or sequence byte is read.  in == out is in place: every lane
+// reads its own two words before it writes them.
+__global__ __launch_bounds__(256) void k_seg_rebase(int64_t n, const int64_t* __restrict__ read_beg, int n_seg,
+                                                    const uint64_t* __restrict__ cig_base,
+                                                    const uint64_t* __restrict__ nib_base, const uint32_t* in_cig,
+                                                    const uint32_t* in_nib, uint32_t* out_cig, uint32_t* out_nib) {
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t w0 = (int64_t)blockIdx.x * 256 + 64 * wave;
+    if (w0 >= n) return;  // (uniform; no barriers in this kernel)
+    const int64_t w1 = w0 + 63 < n ? w0 + 63 : n - 1;
+    const int64_t i = w0 + (threadIdx.x & 63);
+    const int s0 = bcc_seg_of(read_beg, n_seg, w0), s1 = bcc_seg_of(read_beg, n_seg, w1);
+    int seg = s0;
+    if (s0 != s1) seg = bcc_seg_of(read_beg, n_seg, i < n ? i : n - 1);
+    if (i >= n) return;
+    const uint32_t c = in_cig[i], q = in_nib[i];
+    out_cig[i] = bcc_rebase(c, cig_base[seg]);
+    out_nib[i] = bcc_rebase(q, nib_base[seg]);
+}
+
 }  // namespace
+
+hipError_t launch_seg_rebase(hipStream_t s, int64_t n, const int64_t* read_beg, int n_seg, const uint64_t* cig_base,
+                             const uint64_t* nib_base, const uint32_t* in_cig, const uint32_t* in_nib,
+                             uint32_t* out_cig, uint32_t* out_nib) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_seg_rebase, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, read_beg, n_seg, cig_base,
+                       nib_base, in_cig, in_nib, out_cig, out_nib);
+    return hipGetLastError();
+}
 
 hipError_t launch_seg_vpos(hipStream_t s, const int32_t* pos, int64_t n, const int64_t* ref_len,
                            const int64_t* read_beg, const int64_t* voff, int n_seg, int32_t* vpos) {

@@ -269,6 +269,8 @@ def lib() -> C.CDLL:
         "bc_segments_layout": ([vp, C.c_int, vp], C.c_int),
         "bc_pileup_segments": ([vp, C.POINTER(BcReads), C.c_int, vp, vp, vp, i64, vp, u32, C.c_int, dbl, dbl,
                                 vp, vp, vp, vp, vp, vp], C.c_int),
+        "bc_segments_rebase": ([vp, i64, C.c_int, vp, vp, vp, C.c_uint64, C.c_uint64, vp, vp, vp, vp], C.c_int),
+        "bc_amplicons_segments": ([vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, C.c_int32, vp], C.c_int),
         "bc_graph_begin": ([vp], C.c_int),
         "bc_graph_end": ([vp, C.POINTER(vp)], C.c_int),
         "bc_graph_launch": ([vp, vp], C.c_int),
@@ -738,6 +740,20 @@ class Context:
     def amplicons(self, d_cov, d_ent, d_sec, L, d_lo, d_hi, n_tiles, d_out) -> None:
         check(lib().bc_amplicons(self.h, d_cov, d_ent, d_sec, int(L), d_lo, d_hi, int(n_tiles),
                                  d_out))
+
+    def segments_rebase(self, n_reads, n_seg, d_read_beg, d_cig_base, d_nib_base, cig_words_total, nib_total,
+                        d_cig_beg, d_seq_nib, d_cig_beg_out=None, d_seq_nib_out=None) -> None:
+        """bc_segments_rebase: cig_beg / seq_nib of a cohort batch's reads moved by their file's bases
+        (uint64 per segment); in place unless outputs are given."""
+        check(lib().bc_segments_rebase(self.h, int(n_reads), int(n_seg), d_read_beg, d_cig_base, d_nib_base,
+                                       int(cig_words_total), int(nib_total), d_cig_beg, d_seq_nib,
+                                       d_cig_beg if d_cig_beg_out is None else d_cig_beg_out,
+                                       d_seq_nib if d_seq_nib_out is None else d_seq_nib_out))
+
+    def amplicons_segments(self, d_cov, d_ent, d_sec, n_seg, d_ref_len, d_voff, d_lo, d_hi, n_tiles, d_out) -> None:
+        """bc_amplicons_segments: the windows on every segment's own slice, d_out [n_seg][n_tiles][6]."""
+        check(lib().bc_amplicons_segments(self.h, d_cov, d_ent, d_sec, int(n_seg), d_ref_len, d_voff, d_lo, d_hi,
+                                          int(n_tiles), d_out))
 
 
 class Graph:

@@ -960,10 +960,12 @@ class _DeviceFormatter:
         return res
 
 
-def _device_group(ctx, reads, lens, read_beg, mbq, k, nf, nf2, mode, scratch) -> list:
+def _device_group(ctx, reads, lens, read_beg, mbq, k, nf, nf2, mode, scratch, tiles=None) -> list:
     """One launch and one download per output array for a group of references (their lengths
     ``lens``; reads [read_beg[i], read_beg[i + 1]) of ``reads`` are reference i's): each
-    reference's result as _device_reference gives it, sliced on the host."""
+    reference's result as _device_reference gives it, sliced on the host.  ``tiles`` (summary
+    mode, a cohort's --summarise-with-bed): the amplicon windows, the same for every reference;
+    one bc_amplicons_segments launch adds each reference's "amplicons"."""
     n = len(lens)
     voff = D.segments_layout(lens)
     Lv = int(voff[-1])
@@ -978,9 +980,22 @@ def _device_group(ctx, reads, lens, read_beg, mbq, k, nf, nf2, mode, scratch) ->
                         k, nf, nf2, hist.ptr, outs["cov"].ptr, outs["pc"].ptr if rows else None,
                         outs["ent"].ptr, outs["sec"].ptr, d_sum.ptr if d_sum is not None else None)
     if not rows:
+        amp = None
+        if tiles:
+            lo_hi = np.ascontiguousarray(np.asarray(tiles, np.int64).T)  # [2][n_tiles]
+            d_win = scratch.get("amp_lo", lo_hi.nbytes).upload(lo_hi)
+            d_amp = scratch.get("amp", 48 * n * len(tiles))
+            ctx.amplicons_segments(outs["cov"].ptr, outs["ent"].ptr, outs["sec"].ptr, n, d_tab.ptr,
+                                   d_tab.ptr + 8 * (2 * n + 1), d_win.ptr, d_win.ptr + 8 * len(tiles), len(tiles),
+                                   d_amp.ptr)
+            amp = d_amp.download(np.float64, 6 * n * len(tiles)).reshape(n, len(tiles), 6)
         s = d_sum.download(np.float64, 4 * n).reshape(n, 4)
-        return [{"L": int(L), "avg_cov": np.float64(s[i, 0]), "avg_ent": np.float64(s[i, 1]), "nnz": int(s[i, 2])}
-                for i, L in enumerate(lens)]
+        res = [{"L": int(L), "avg_cov": np.float64(s[i, 0]), "avg_ent": np.float64(s[i, 1]), "nnz": int(s[i, 2])}
+               for i, L in enumerate(lens)]
+        for i, L in enumerate(lens if tiles is not None else ()):
+            res[i]["amplicons"] = ((amp[i], [max(a, 0) > min(b, int(L) - 1) for a, b in tiles]) if tiles
+                                   else (np.zeros((0, 6)), []))
+        return res
     texts = [None] * n
     if scratch.formatter is not None:  # the text where the arrays lie; None: a declined value
         texts = scratch.formatter.group(lens, voff, hist, outs, Lv)

@@ -368,6 +368,44 @@ int bc_pileup_segments(bc_ctx* ctx, const bc_reads* d_reads, int n_seg, const in
                        uint32_t min_base_quality, int k, double nf, double nf2, int32_t* d_counts, int32_t* d_cov,
                        double* d_pc, double* d_ent, double* d_sec, double* d_sum /* [n_seg][4] or NULL */);
 
+/* Several FILES in one launch (a cohort: thousands of amplicon samples of one small genome).  The
+ * selected reads of the files lie side by side in shared device buffers and every (file, reference)
+ * pair is one segment of bc_pileup_segments.  Two calls complete that picture; both are
+ * stream-ordered, allocate nothing, never synchronise and can be captured in a graph, and both
+ * check their arguments (BC_E_ARG) before any device is touched.
+ *
+ * bc_segments_rebase.  File f's CIGAR words were copied to word offset cig_base of the shared
+ * CIGAR buffer, its BC_SEQ_EVENT bytes (and its qualities, indexed by nibble) to a byte offset that
+ * is a multiple of 16, nib_base = 2 x that offset.  Its reads' cig_beg / seq_nib still count from
+ * the file's own arrays.  One launch (k_seg_rebase, one lane per read) finds each read's segment in
+ * d_read_beg [n_seg + 1] (as bc_pileup_segments takes it) and writes
+ *     d_cig_beg_out[i] = d_cig_beg[i] + d_cig_base[seg],  d_seq_nib_out[i] = d_seq_nib[i] + d_nib_base[seg]
+ * in uint32; d_cig_base / d_nib_base: uint64 [n_seg], one entry per SEGMENT (a file's segments
+ * repeat the file's bases).  In place when the output pointers equal the input pointers; any
+ * other overlap of the four arrays is a caller error.  No CIGAR or sequence byte is read.
+ * cig_words_total / nib_total: the shared buffers' sizes in CIGAR words and in nibbles (2 x the
+ * sequence bytes); BC_E_ARG when either reaches 2^32, for then a sum could wrap.  The caller
+ * guarantees value + base < total for every read.  BC_E_ARG also for n_reads outside [0, 2^31),
+ * n_seg < 1 and NULL arrays (the per-read arrays may be NULL when n_reads == 0).
+ * Timed as BC_K_INDEX.
+ *
+ * bc_amplicons_segments.  The windows [d_lo[t], d_hi[t]] (inclusive, t < n_tiles) applied to every
+ * segment of a virtual reference laid out by bc_segments_layout (d_ref_len [n_seg], d_voff
+ * [n_seg + 1] or longer): d_out[seg][t][0..6) = mean_cov, median_cov, mean_ent, median_ent,
+ * mean_sec, median_sec, bit for bit what bc_amplicons gives on segment seg's slice
+ * [voff[seg], voff[seg] + ref_len[seg]) with ref_len[seg] as its L: the window is clipped to the
+ * segment's own [0, ref_len - 1], an empty window gives -1.0 six times, and no pad or neighbouring
+ * segment is ever read.  One launch (k_amplicon_segments) of n_seg x n_tiles workgroups with
+ * k_amplicon's arithmetic.  n_tiles == 0 does nothing.  BC_E_ARG for n_seg < 1, n_tiles < 0,
+ * n_seg x n_tiles >= 2^31 and NULL arrays.  Timed as BC_K_AMPLICONS.                             */
+int bc_segments_rebase(bc_ctx* ctx, int64_t n_reads, int n_seg, const int64_t* d_read_beg,
+                       const uint64_t* d_cig_base, const uint64_t* d_nib_base, uint64_t cig_words_total,
+                       uint64_t nib_total, const uint32_t* d_cig_beg, const uint32_t* d_seq_nib,
+                       uint32_t* d_cig_beg_out, uint32_t* d_seq_nib_out);
+int bc_amplicons_segments(bc_ctx* ctx, const int32_t* d_cov, const double* d_ent, const double* d_sec, int n_seg,
+                          const int64_t* d_ref_len, const int64_t* d_voff, const int64_t* d_lo,
+                          const int64_t* d_hi, int32_t n_tiles, double* d_out /* [n_seg][n_tiles][6] */);
+
 /* hipGraph capture of a sequence of compute calls on the context's stream (the context must own
  * its stream or have been given a non-default one).  bc_graph_end instantiates the graph;
  * bc_graph_launch replays it on the context's stream.                                         */

@@ -1,6 +1,9 @@
 """Per-kernel register / LDS usage of one HIP source for gfx950 (the compiler's
 kernel-resource-usage remarks), one line per kernel:
-    python scripts/resources.py basecount_amd/csrc/bc_rc.hip [extra hipcc flags]"""
+    python scripts/resources.py basecount_amd/csrc/bc_rc.hip [extra hipcc flags]
+The cohort kernels (DESIGN.md §3 "Cohort runs"): k_seg_rebase is in bc_segments.hip,
+k_amplicon_segments next to k_amplicon in bc_kernels.hip (add -Ibasecount_amd/csrc when the source
+is a copy outside that directory)."""
 import re
 import subprocess
 import sys
