@@ -16,7 +16,9 @@
 constexpr unsigned long long kNibCol6 = 0x6666666366625106ull;  // class -> column, 6 = none
 constexpr uint32_t kClsDel = 0xCCCCCCCCu;  // class 1100 (deletion / ref-skip) in every nibble
 constexpr uint32_t kNone = 0xFFFFFFFFu;  // packed event: none
-constexpr uint32_t kDel = 0x80000000u;   // packed event: deletion / ref-skip
+// packed event: deletion / ref-skip.  Every value below it is a base's nibble index (sequence above
+// nibble 2^31 included: a buffer of up to 2^31 - 1 bytes)
+constexpr uint32_t kDel = 0xFFFFFFFEu;
 
 __device__ __forceinline__ unsigned nib_col6(unsigned nib) { return (unsigned)(kNibCol6 >> (nib * 4)) & 0xFu; }
 __device__ __forceinline__ uint32_t rdl(uint32_t v, int l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, l); }
@@ -278,6 +280,20 @@ __device__ __forceinline__ void stage_wait() { asm volatile("s_waitcnt vmcnt(0)"
 // Where a walk reads its event classes: the chunk's stage in LDS (nibble indices relative to the
 // stage; one readable pad word before and after, lim = last word index) or the whole
 // BC_SEQ_EVENT buffer in HBM (lim = readable words).  Qualities only for unstaged walks.
+//
+// An unstaged record keeps its base index as 32 bits: the nibble index in the whole buffer of the
+// base at a run's reference offset 0 (or at the tile's first position), which lies up to a read's
+// span + a tile below the read's first base (so it can be negative) and below 2^32.  unstaged_index
+// widens index + window offset over [-kNbBias, 2^32 - kNbBias): exact for every buffer shorter than
+// 2^31 - kNbBias bytes, where a plain sign extension sent every base above nibble 2^31 to a zero fetch.
+// WIDE: the sign word by a compare, the offset added after it (the same value; which form costs
+// fewer registers differs between the instances at the 128-VGPR limit).
+constexpr uint32_t kNbBias = 16384;  // > 0x1FFF (the longest simple read's span) + 2 tiles
+template <bool WIDE = false>
+__device__ __forceinline__ int64_t unstaged_index(uint32_t nb, int off) {
+    if (WIDE) return (int64_t)(((uint64_t)(nb >= 0u - kNbBias ? 0xFFFFFFFFu : 0u) << 32) | nb) + off;
+    return (int64_t)(nb + (uint32_t)(off + (int)kNbBias)) - (int64_t)kNbBias;
+}
 struct SeqSrc {
     const uint32_t* words;
     int64_t lim;
@@ -352,7 +368,7 @@ __device__ __forceinline__ uint32_t window_events(const SeqSrc& S, const uint4* 
 #pragma unroll
     for (int k = 0; k < NR; ++k) {
         const uint32_t m = range_mask((int)(rr[k] & 0xFFFFu), (int)(rr[k] >> 16), j4);
-        const int64_t n0 = STAGED ? (int64_t)((int)nb[k] + j0) : (int64_t)(int32_t)nb[k] + j0;
+        const int64_t n0 = STAGED ? (int64_t)((int)nb[k] + j0) : unstaged_index<QUAL>(nb[k], j0);
         uint32_t v = fetch8<STAGED>(S, n0);
         if (QUAL && !STAGED) v &= qual_mask_at(S, n0);
         x |= v & m;
@@ -369,7 +385,7 @@ __device__ __forceinline__ uint32_t window_events(const SeqSrc& S, const uint4* 
 // and `nb`, the index of the base the read has at the tile's first position (the run's base at
 // reference offset t0 - pos): staged, 4 x the nibble index relative to the stage (a bit index: its
 // low 5 bits are the funnel shift of every window of the read); unstaged, the nibble index in the
-// whole BC_SEQ_EVENT buffer (int32, widened by the fetch).  A window (lane constant c32 =
+// whole BC_SEQ_EVENT buffer (32 bits, widened by the fetch: unstaged_index).  A window (lane constant c32 =
 // 32 * (lane >> 3)) subtracts c32, clamps to [0, 32] and builds the mask.
 //   single-run chunks (NR = 1), one uint4:  {lo4, hi4, nb, gp}     (plain int32, not clamped)
 //   NR = 2, 4, three uint4:  [0] = {gp, 0, rr0, nb0}  [1] = {rr1, nb1, rr2, nb2}  [2] = {rr3, nb3, 0, 0}
@@ -397,8 +413,7 @@ __device__ __forceinline__ uint32_t tile_fetch(const SeqSrc& S, uint32_t nb, int
         w0 = w0 < -1 ? -1 : (w0 > lim ? lim : w0);
         return __builtin_amdgcn_alignbit(S.words[w0 + 1], S.words[w0], (uint32_t)b);
     }
-    const int64_t n0 = (int64_t)(int32_t)nb + (c32 >> 2);
-    return fetch8<false>(S, n0);
+    return fetch8<false>(S, unstaged_index(nb, c32 >> 2));
 }
 
 // The 8 event classes (x) read r has in the lane's window: its M runs' bases (one funnel-shifted
