@@ -276,7 +276,16 @@ int bc_reads_free(bc_ctx* ctx, bc_reads* d_reads);
  * per-read arrays written in start order and each read's aligned sequence (and qualities) copied
  * so that consecutive reads have consecutive sequence again.  The copy shares d_reads' CIGAR
  * buffer; everything else lives in d_mem (bc_reads_sort_bytes bytes, 256-byte aligned), which
- * must outlive its use.  *d_sorted is then a sorted batch (sorted = 1, same max_span / max_end,
+ * must outlive its use -- with one exception, the FIELDS-ONLY view: a batch without qualities
+ * (d_reads->qual == NULL) that, once sorted, this context's shape would give to the read-chunked
+ * k_rc on a reference of max_end positions (shape "rc" / "ops"; under any shape a max_span
+ * above 4,096; under "auto" n_reads * (max_span + 63) / max_end >= 2,048) and that the bucketed
+ * sort takes (max_end + 2 <= 2^24) has only its four per-read arrays sorted.  Then d_sorted->seq
+ * == d_reads->seq and seq_nib still indexes it: d_reads' SEQUENCE buffer, like its CIGAR buffer,
+ * must outlive *d_sorted (compare the two pointers to tell; a batch with qualities and the
+ * counting sort of a longer reference always copy).  The decision uses max_end and the shape in
+ * force at the call, not the reference length or shape of the later kernels: every kernel takes
+ * either kind of view.  *d_sorted is then a sorted batch (sorted = 1, same max_span / max_end,
  * no index: build one with bc_reads_index) that every kernel takes, with the same counts as the
  * input (count.cpp's sums do not depend on the read order).  Needs seq_layout == BC_SEQ_EVENT
  * and seq_bytes + 5 n_reads + 16 <= 0x55555550 (BC_E_ARG otherwise: split the batch).

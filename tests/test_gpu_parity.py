@@ -12,9 +12,11 @@ import numpy as np
 import pytest
 
 import oracle as O
+import sort_plans as SP
 from basecount_amd import device as D
 from basecount_amd import synth
 from basecount_amd.main import norm_factors
+from test_gpu_sort_plans import source_copy, view_copy
 
 pytestmark = pytest.mark.gpu
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -482,15 +484,17 @@ def test_device_sort_read_longer_than_16_bits(ctx):
 def test_device_sort_flags_are_deferred(ctx):
     """bc_reads_sort only enqueues: a batch whose max_end is not truthful (a start past it) sorts
     without an error at the call, and bc_reads_sort_check then reports the bad start (BC_E_ARG);
-    a truthful batch checks clean."""
+    a truthful batch checks clean.  Both views hold the batch's reads (sort_plans.sorted_view_matches),
+    the flagged one with the offending starts at 0."""
     rng = np.random.default_rng(95)
     L, n = 4_000, 5_000
     b = random_batch(rng, L, n, sort=False)
     r = D.DeviceReads(ctx, b)
     nb = ctx.sort_bytes(r)
     mem = ctx.alloc(nb)
-    ctx.sort(r, mem.ptr, nb, check_flags=False)
+    s0 = ctx.sort(r, mem.ptr, nb, check_flags=False)
     ctx.sort_check(r, mem.ptr)  # clean
+    SP.sorted_view_matches(source_copy(ctx, r.r), view_copy(ctx, r.r, s0))
     bad = D.BcReads.from_buffer_copy(r.r)
     bad.max_end = 1_000  # starts beyond it exist
     nb2 = ctx.sort_bytes(bad)
@@ -499,6 +503,11 @@ def test_device_sort_flags_are_deferred(ctx):
     assert s.sorted == 1  # (no error at the call: the device has not run yet)
     with pytest.raises(D.BcError, match="outside"):
         ctx.sort_check(bad, mem2.ptr)
+    # the flagged view stays safe to count: the batch's reads, those starting past max_end at 0
+    src = source_copy(ctx, bad)
+    assert np.count_nonzero(src["pos"] > 1_000) > 1_000
+    src["pos"][src["pos"] > 1_000] = 0
+    SP.sorted_view_matches(src, view_copy(ctx, bad, s))
     for x in (mem, mem2):
         x.free()
     r.free()
