@@ -868,7 +868,9 @@ int bc_pileup_plan(const bc_reads* r, int64_t ref_len, int shape, int tile_waves
 
 int bc_ctx_set_instance(bc_ctx* c, int instance) {
     if (!c) return fail(BC_E_ARG, "ctx is NULL");
-    if (instance < BC_INSTANCE_AUTO || instance > BC_INSTANCE_LEAN) return fail(BC_E_ARG, "unknown BC_INSTANCE_* value");
+    if (instance != BC_INSTANCE_AUTO && instance != BC_INSTANCE_GENERAL && instance != BC_INSTANCE_LEAN &&
+        instance != BC_INSTANCE_SLICE)
+        return fail(BC_E_ARG, "unknown BC_INSTANCE_* value");
     c->instance = instance;
     return BC_OK;
 }
@@ -880,7 +882,9 @@ int bc_pileup_launch_info(const bc_reads* r, int64_t ref_len, int shape, int til
     if (shape < BC_SHAPE_AUTO || shape > BC_SHAPE_OPS) return fail(BC_E_ARG, "unknown BC_SHAPE_* value");
     if (tile_waves != 0 && tile_waves != 1 && tile_waves != 2 && tile_waves != 4 && tile_waves != 8)
         return fail(BC_E_ARG, "tile_waves must be 0, 1, 2, 4 or 8");
-    if (instance < BC_INSTANCE_AUTO || instance > BC_INSTANCE_LEAN) return fail(BC_E_ARG, "unknown BC_INSTANCE_* value");
+    if (instance != BC_INSTANCE_AUTO && instance != BC_INSTANCE_GENERAL && instance != BC_INSTANCE_LEAN &&
+        instance != BC_INSTANCE_SLICE)
+        return fail(BC_E_ARG, "unknown BC_INSTANCE_* value");
     if (k != 5 && k != 6) return fail(BC_E_ARG, "k must be 5 or 6");
     bc::pileup_launch_info(*r, ref_len, shape, tile_waves, instance, mbq, k, *out);
     return BC_OK;

@@ -136,8 +136,11 @@ __device__ __forceinline__ void tile_tail(const ARGS& A, lds_u32* f, lds_f64* ta
 // LEAN: the register- and LDS-lean instance (process_chunk: the one-run window walk, every other
 // read alone in walk_complex) at five waves per SIMD instead of four; exact on any batch, ahead
 // while slow reads are few (launch_pileup_tiles routes).
-template <bool QUAL, int K, bool STATS, typename IT, bool LEAN = false>
-__global__ __launch_bounds__(512, LEAN ? 5 : 4) void k_pileup(TileArgs A) {
+// SLICE (with LEAN): the lean walk over per-read slices (process_chunk, bc_slice.h): 4 KiB of
+// stage per wave whatever the read length, and six waves per SIMD.
+template <bool QUAL, int K, bool STATS, typename IT, bool LEAN = false, bool SLICE = false>
+__global__ __launch_bounds__(512, SLICE ? 6 : LEAN ? 5 : 4) void k_pileup(TileArgs A) {
+    static_assert(!SLICE || (LEAN && !QUAL && sizeof(IT) == 4), "slice instances: lean, no threshold, 32-bit indices");
     extern __shared__ __attribute__((aligned(16))) unsigned char dyn[];
     __shared__ IT rng[8][2];  // per group: the tile's read range
     if (BC_ABL(A) & 64) return;
@@ -149,7 +152,7 @@ __global__ __launch_bounds__(512, LEAN ? 5 : 4) void k_pileup(TileArgs A) {
     const int g = wave / S, ws = wave - g * S;
     const int groups = nw / S;
     constexpr int rec_bytes = LEAN ? kLeanRecBytes : kRecBytes;
-    constexpr int stage_region = LEAN ? kLeanStageRegion : kStageRegion;
+    constexpr int stage_region = SLICE ? kSliceStageRegion : LEAN ? kLeanStageRegion : kStageRegion;
     uint4* rec_all = (uint4*)dyn;
     uint8_t* stage_all = dyn + (size_t)nw * rec_bytes;
     uint32_t(*fin)[6][kTile] = (uint32_t(*)[6][kTile])(stage_all + (size_t)nw * stage_region);
@@ -205,7 +208,11 @@ __global__ __launch_bounds__(512, LEAN ? 5 : 4) void k_pileup(TileArgs A) {
                 hi = rg.y;
             } else {
                 int64_t l64, h64;
-                lower_bound_pair(A.pos, A.n, (int64_t)t0 - A.max_span + 1, (int64_t)t0 + kTile, lane, l64, h64);
+                int sl = lane;
+                // (SLICE: the search's lane-derived operands are computed here, not hoisted out of
+                // the tile loop into registers the six-wave budget does not have)
+                if constexpr (SLICE) asm volatile("" : "+v"(sl));
+                lower_bound_pair(A.pos, A.n, (int64_t)t0 - A.max_span + 1, (int64_t)t0 + kTile, sl, l64, h64);
                 lo = (IT)l64;
                 hi = (IT)h64;
             }
@@ -247,7 +254,7 @@ __global__ __launch_bounds__(512, LEAN ? 5 : 4) void k_pileup(TileArgs A) {
 #endif
             for (; base < hi; base += (IT)S * 64) {
                 const IT nb = base + (IT)S * 64;
-                process_chunk<QUAL, K, PLANES, LEAN>(A, base, chunk_nr(base), F, nb, chunk_nr(nb), lane, s8, gb, t0, P,
+                process_chunk<QUAL, K, PLANES, LEAN, SLICE>(A, base, chunk_nr(base), F, nb, chunk_nr(nb), lane, s8, gb, t0, P,
                                                      edge, beyond, bmask, myrec, mystage, qual_vec, W, cnt, acc,
                                                      pending, bad);
                 __builtin_amdgcn_wave_barrier();
@@ -587,7 +594,7 @@ struct TileShape {
     int64_t blocks;
     size_t lds;      // dynamic
 };
-TileShape tile_shape(int64_t n_tiles, int S, bool lean = false) {
+TileShape tile_shape(int64_t n_tiles, int S, int inst = kInstGeneral) {
     TileShape t;
     t.nw = S >= 4 ? S : 4;
     t.groups = t.nw / S;
@@ -595,7 +602,7 @@ TileShape tile_shape(int64_t n_tiles, int S, bool lean = false) {
     const int64_t cap = 256 * 64;
     if (t.blocks > cap) t.blocks = cap;
     t.blocks = (t.blocks + 7) / 8 * 8;  // a multiple of the XCD count (see the kernel's tile mapping)
-    t.lds = pileup_lds_bytes(t.nw, t.groups, lean);
+    t.lds = pileup_lds_bytes(t.nw, t.groups, inst);
     return t;
 }
 
@@ -603,23 +610,30 @@ TileShape tile_shape(int64_t n_tiles, int S, bool lean = false) {
 // The lean instance is built where it holds five waves per SIMD (at most 96 VGPRs, nothing
 // spilled: scripts/resources.py); every other combination has the
 // general instance alone.
+// The slice instance is built where the LDS-DMA staging runs and the planes walk is taken: no
+// quality threshold, 32-bit indices (four kernels: k = 5, 6 with and without statistics), each at
+// six waves per SIMD (at most 80 VGPRs, nothing spilled: round 11).
 constexpr bool lean_built(bool qual, bool i32) { return !qual || i32; }
+constexpr bool slice_built(bool qual, bool i32) { return !qual && i32; }
 typedef void (*TileKernel)(TileArgs);
 template <bool Q, int KK, bool ST, typename IT>
-TileKernel tile_kernel_of(bool lean) {
+TileKernel tile_kernel_of(int inst) {
+    if constexpr (slice_built(Q, sizeof(IT) == 4)) {
+        if (inst == kInstSlice) return k_pileup<Q, KK, ST, IT, true, true>;
+    }
     if constexpr (lean_built(Q, sizeof(IT) == 4)) {
-        if (lean) return k_pileup<Q, KK, ST, IT, true>;
+        if (inst == kInstLean) return k_pileup<Q, KK, ST, IT, true>;
     }
     return k_pileup<Q, KK, ST, IT, false>;
 }
 template <bool Q, int KK>
-TileKernel tile_kernel_qk(bool stats, bool i32, bool lean) {
-    if (stats) return i32 ? tile_kernel_of<Q, KK, true, int32_t>(lean) : tile_kernel_of<Q, KK, true, int64_t>(lean);
-    return i32 ? tile_kernel_of<Q, KK, false, int32_t>(lean) : tile_kernel_of<Q, KK, false, int64_t>(lean);
+TileKernel tile_kernel_qk(bool stats, bool i32, int inst) {
+    if (stats) return i32 ? tile_kernel_of<Q, KK, true, int32_t>(inst) : tile_kernel_of<Q, KK, true, int64_t>(inst);
+    return i32 ? tile_kernel_of<Q, KK, false, int32_t>(inst) : tile_kernel_of<Q, KK, false, int64_t>(inst);
 }
-TileKernel tile_kernel(bool qual, int k, bool stats, bool i32, bool lean) {
-    if (qual) return k == 5 ? tile_kernel_qk<true, 5>(stats, i32, lean) : tile_kernel_qk<true, 6>(stats, i32, lean);
-    return k == 5 ? tile_kernel_qk<false, 5>(stats, i32, lean) : tile_kernel_qk<false, 6>(stats, i32, lean);
+TileKernel tile_kernel(bool qual, int k, bool stats, bool i32, int inst) {
+    if (qual) return k == 5 ? tile_kernel_qk<true, 5>(stats, i32, inst) : tile_kernel_qk<true, 6>(stats, i32, inst);
+    return k == 5 ? tile_kernel_qk<false, 5>(stats, i32, inst) : tile_kernel_qk<false, 6>(stats, i32, inst);
 }
 // > 64 KiB of dynamic LDS must be allowed per kernel (160 KiB per CU on gfx950), once
 void allow_lds(TileKernel fn) {
@@ -639,10 +653,20 @@ void allow_lds(TileKernel fn) {
 // instance unless every read of the buffer has one op (kLeanMaxSlowShare is zero: measured).
 bool tile_lean(const bc_reads& r, bool qual, bool i32, int instance) {
     if (!lean_built(qual, i32) || instance == BC_INSTANCE_GENERAL) return false;
-    if (instance == BC_INSTANCE_LEAN) return true;
+    if (instance == BC_INSTANCE_LEAN || instance == BC_INSTANCE_SLICE) return true;
     const int64_t extra = r.n_cigar_words - r.n_reads;
     const double slow_max = extra > 0 ? (double)extra / 2.0 : 0.0;
     return slow_max <= kLeanMaxSlowShare * (double)r.n_reads;
+}
+// The instance launched (TileInstance).  The slice instance is the lean walk at six workgroups per
+// CU instead of five, and it stages a read's 64-B slice once per tile where the lean instance
+// stages the whole read: BC_INSTANCE_AUTO takes it wherever it takes the lean walk, a slice
+// instance is built, and a read can be longer than a tile (max_span > kTile: only then is a slice
+// less than the read).  Forced where none is built it falls back as a forced lean instance does.
+int tile_instance(const bc_reads& r, bool qual, bool i32, int instance) {
+    if (!tile_lean(r, qual, i32, instance)) return kInstGeneral;
+    if (!slice_built(qual, i32) || instance == BC_INSTANCE_LEAN) return kInstLean;
+    return (instance == BC_INSTANCE_SLICE || r.max_span > kTile) ? kInstSlice : kInstLean;
 }
 
 // the sparse sweep's: tiles per wave and workgroups of kSoloWaves waves (sump: whole quarter
@@ -734,16 +758,16 @@ void pileup_launch_info(const bc_reads& r, int64_t L, int shape, int tile_waves,
     const int64_t reach = r.max_end > L ? r.max_end : L;
     const int64_t n_tiles = (reach + kTile - 1) / kTile;
     const bool i32 = tiles_fit_i32(r.n_reads, n_tiles, r.max_span);
-    const bool lean = tile_lean(r, mbq > 0, i32, instance);
-    const TileShape t = tile_shape(n_tiles, p.waves_per_tile, lean);
-    o.lean = lean ? 1 : 0;
+    const int inst = tile_instance(r, mbq > 0, i32, instance);
+    const TileShape t = tile_shape(n_tiles, p.waves_per_tile, inst);
+    o.lean = inst != kInstGeneral ? 1 : 0;
     o.lds_bytes = (int32_t)(t.lds + 8 * 2 * (i32 ? 4 : 8));  // + rng, the static range hand-off
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
         (void)hipGetLastError();
         return;
     }
-    const TileKernel fn = tile_kernel(mbq > 0, k, true, i32, lean);
+    const TileKernel fn = tile_kernel(mbq > 0, k, true, i32, inst);
     allow_lds(fn);
     int nb = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)fn, o.block_threads, t.lds) == hipSuccess)
@@ -822,8 +846,8 @@ hipError_t launch_pileup_tiles(hipStream_t s, const bc_reads& r, int64_t L, int6
         return hipGetLastError();
     }
     const bool i32 = tiles_fit_i32(A.n, A.n_tiles, A.max_span);
-    const bool lean = tile_lean(r, mbq > 0, i32, instance);
-    const TileShape ts = tile_shape(A.n_tiles, S, lean);
+    const int inst = tile_instance(r, mbq > 0, i32, instance);
+    const TileShape ts = tile_shape(A.n_tiles, S, inst);
     const int nw = ts.nw;
     const int64_t blocks = ts.blocks;
     const dim3 grid((unsigned)blocks), block(64 * nw);
@@ -843,7 +867,7 @@ hipError_t launch_pileup_tiles(hipStream_t s, const bc_reads& r, int64_t L, int6
         if (tn <= (size_t)256 * 64 * 16 * kTracePhases) A.trace = tbuf;
     }
     const TileArgs T = A;  // k_pileup takes the walk's fields only
-    const TileKernel fn = tile_kernel(mbq > 0, k, stats, i32, lean);
+    const TileKernel fn = tile_kernel(mbq > 0, k, stats, i32, inst);
     allow_lds(fn);
     hipLaunchKernelGGL(fn, grid, block, lds, s, T);
     if (A.trace && ++tcalls == 20) {

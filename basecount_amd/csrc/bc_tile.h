@@ -8,6 +8,7 @@
 
 #include "bc_internal.h"
 #include "bc_log2.h"
+#include "bc_slice.h"
 #include "bc_stats.h"
 
 namespace bc {
@@ -393,9 +394,22 @@ constexpr int kLeanStageRegion = kLeanStage + 32;
 static_assert(5 * ((4 * (kLeanRecBytes + kLeanStageRegion) + kFinBytes + kLog2TabBytes + 64 + kLdsGranule - 1) /
                    kLdsGranule * kLdsGranule) <= 160 * 1024,
               "5 lean four-wave blocks per CU");
-__host__ __device__ inline size_t pileup_lds_bytes(int nw, int groups, bool lean = false) {
-    return (size_t)nw * (lean ? kLeanRecBytes + kLeanStageRegion : kRecBytes + kStageRegion) +
-           (size_t)groups * kFinBytes + kLog2TabBytes;
+// The slice instance (k_pileup<.., LEAN, SLICE>: the lean walk over per-read slices, bc_slice.h):
+// the lean records and a stage of 64 slots of 64 B, so that SIX four-wave blocks of one tile fit
+// (6 x 24,320 B after rounding).
+constexpr int kSliceStage = bc_slice::kStageBytes;
+constexpr int kSliceStageRegion = kSliceStage + 32;
+static_assert(bc_slice::kTile == kTile && bc_slice::kSlots == 64, "a slot per read of a chunk, a tile of kTile positions");
+static_assert(6 * ((4 * (kLeanRecBytes + kSliceStageRegion) + kFinBytes + kLog2TabBytes + 64 + kLdsGranule - 1) /
+                   kLdsGranule * kLdsGranule) <= 160 * 1024,
+              "6 slice four-wave blocks per CU");
+// k_pileup's instances
+enum TileInstance { kInstGeneral = 0, kInstLean = 1, kInstSlice = 2 };
+__host__ __device__ inline size_t pileup_lds_bytes(int nw, int groups, int inst = kInstGeneral) {
+    const int per_wave = inst == kInstSlice  ? kLeanRecBytes + kSliceStageRegion
+                         : inst == kInstLean ? kLeanRecBytes + kLeanStageRegion
+                                             : kRecBytes + kStageRegion;
+    return (size_t)nw * per_wave + (size_t)groups * kFinBytes + kLog2TabBytes;
 }
 
 // Per-read fields of a chunk (lane = read), loaded one chunk ahead of their use.
@@ -468,14 +482,24 @@ constexpr uint32_t kSpecSlack = 128;  // bytes staged beyond the last read's fir
 // ballot of the chunk's slow reads.  A chunk whose fast reads' segment does not fit the stage
 // after the exact restage is walked by walk_complex as a whole.  The counts and the first
 // offending read (a minimum over read indices) are those of the general instance.
-template <bool QUAL, int K, bool PLANES, bool LEAN = false>
+//
+// SLICE (k_pileup's slice instance, LEAN with it): the stage is 64 slots of 64 B, one per read,
+// each holding the 64 B of sequence this TILE can read of it (bc_slice.h).  The slots are filled
+// by LDS-DMA with per-lane sources, lane = (read lane >> 2, piece lane & 3): one instruction
+// writes 16 whole slots, a chunk takes four.  They are issued with the CIGAR loads from the fields
+// alone (a run that starts at query offset 0 assumed), so a chunk still costs one memory round
+// trip; a read whose decoded run needs a base outside its slot (a leading insertion longer than the
+// slot's slack) is walked as a slow read.  Nothing chunk-wide is reduced: a slice chunk always
+// stages, whatever the reads' length or the order of their sequence.
+template <bool QUAL, int K, bool PLANES, bool LEAN = false, bool SLICE = false>
 __device__ __forceinline__ void process_chunk(const TileArgs& A, int64_t base, int nr, ReadFields& F,
                                               int64_t next_base, int next_nr, int lane, int s8, int gb, int64_t t0,
                                               int64_t P, bool edge, bool beyond, uint32_t bmask, uint4* myrec,
                                               uint8_t* mystage, bool qual_vec, typename WalkCounters<PLANES>::type& W,
                                               uint32_t (&cnt)[6],
                                               unsigned long long& acc, int& pending, int64_t& bad) {
-    constexpr int STG = LEAN ? kLeanStage : kStage;  // the stage's capacity
+    static_assert(!SLICE || (LEAN && PLANES && !QUAL), "the slice instance is the lean planes walk");
+    constexpr int STG = SLICE ? kSliceStage : LEAN ? kLeanStage : kStage;  // the stage's capacity
     constexpr int RS = LEAN ? 1 : 3;                 // uint4 per record
     // ---- chunk load: CIGAR -> run table (VALU), speculative staging in flight meanwhile
     RunTable T;
@@ -498,7 +522,18 @@ __device__ __forceinline__ void process_chunk(const TileArgs& A, int64_t base, i
     const bool dma = !QUAL && !(BC_ABL(A) & 32);
     uint32_t spec_lo = 0, spec_hi = 0;
     bool spec = false;
-    if (dma && !(BC_ABL(A) & 512)) {
+    if constexpr (SLICE) {
+        // the lane's read's first source byte; the buffer's readable end
+        const uint32_t slot_end = (uint32_t)(A.seq_words * 4 < 0xFFFFFFFFll ? A.seq_words * 4 : 0xFFFFFFF0ll);
+        const uint32_t slot_src = bc_slice::source_byte(msn, (int32_t)(mpos - (uint32_t)t0));
+        const uint32_t piece = (uint32_t)(lane & 3) * (uint32_t)bc_slice::kPieceBytes;
+        for (int e = 0; 16 * e < nr; ++e) {  // (uniform) 16 reads' slots per instruction
+            const int r = 16 * e + (lane >> 2);
+            const uint32_t src = (uint32_t)__shfl((int)slot_src, r) + piece;
+            if (r < nr && src < slot_end)  // bc_slice::piece_issued
+                __builtin_amdgcn_global_load_lds((gbl_void_t*)(A.seq + src), (lds_void_t*)(mystage + 1024 * e), 16, 0, 0);
+        }
+    } else if (dma && !(BC_ABL(A) & 512)) {
         const uint32_t buf_end = (uint32_t)(A.seq_words * 4 < 0xFFFFFFFFll ? A.seq_words * 4 : 0xFFFFFFF0ll);
         spec_lo = (rdl(msn, 0) >> 1) & ~15u;
         spec_hi = (rdl(msn, nr - 1) >> 1) + kSpecSlack;
@@ -508,22 +543,36 @@ __device__ __forceinline__ void process_chunk(const TileArgs& A, int64_t base, i
     }
     if (lane < nr) T = LEAN ? decode_runs<1>(w, mcn, cmax) : decode_runs(w, mcn, cmax);
     // LEAN: no chunk-wide property is reduced; `slow` is the lane's own read
-    const bool slow = LEAN && (T.complex || T.gap || T.nrun > 1);
+    // SLICE: the slot's source byte again (not kept in a register through the decode), and whether
+    // the slot holds what the decoded run needs
+    int32_t srel = 0;
+    uint32_t slot_src = 0;
+    bool miss = false;
+    if constexpr (SLICE) {
+        uint32_t sn2 = msn;
+        asm volatile("" : "+v"(sn2));
+        srel = (int32_t)(mpos - (uint32_t)t0);
+        slot_src = bc_slice::source_byte(sn2, srel);
+        const uint32_t slot_end = (uint32_t)(A.seq_words * 4 < 0xFFFFFFFFll ? A.seq_words * 4 : 0xFFFFFFF0ll);
+        miss = !bc_slice::covered(msn, srel, T.st[0], T.en[0], T.qd[0], slot_src, slot_end);
+    }
+    const bool slow = LEAN && (T.complex || T.gap || T.nrun > 1 || (SLICE && miss));
     const bool cx = LEAN ? false : __any(T.complex);
     const bool gap = LEAN ? false : __any(T.gap);
     const int maxrun = LEAN ? 1 : (int)wave_reduce<true>((uint32_t)T.nrun);
     // ---- the chunk's exact sequence segment (BC_SEQ_EVENT bytes; LEAN: of its fast reads)
     uint32_t blo = 0xFFFFFFFFu, bhi = 0;
-    if (lane < nr && T.qlen && !slow) {
+    if (!SLICE && lane < nr && T.qlen && !slow) {
         blo = msn >> 1;
         bhi = (msn + T.qlen + 1) >> 1;
     }
-    uint32_t seg_lo = wave_reduce<false>(blo);
-    const uint32_t seg_hi = wave_reduce<true>(bhi);
+    uint32_t seg_lo = SLICE ? 0u : wave_reduce<false>(blo);
+    const uint32_t seg_hi = SLICE ? 0u : wave_reduce<true>(bhi);
     seg_lo = seg_hi > seg_lo ? (seg_lo & ~15u) : 0u;
-    const bool spec_ok = spec && !cx && (seg_hi <= seg_lo || (seg_lo >= spec_lo && seg_hi <= spec_hi));
+    // (SLICE: every read's slot is in the stage already)
+    const bool spec_ok = SLICE || (spec && !cx && (seg_hi <= seg_lo || (seg_lo >= spec_lo && seg_hi <= spec_hi)));
     if (spec_ok) seg_lo = spec_lo;  // the stage holds [spec_lo, spec_hi)
-    const bool staged = !cx && (spec_ok || seg_hi - seg_lo <= (uint32_t)STG) && !(BC_ABL(A) & 32);
+    const bool staged = SLICE || (!cx && (spec_ok || seg_hi - seg_lo <= (uint32_t)STG) && !(BC_ABL(A) & 32));
     // LEAN: the reads walk_complex takes (wave-uniform; all of them when nothing is staged)
     const unsigned long long slow_list = LEAN ? __ballot(lane < nr && (slow || !staged)) : 0ull;
     if (spec && !spec_ok) stage_wait();  // the speculative copy must land before it is overwritten
@@ -532,7 +581,13 @@ __device__ __forceinline__ void process_chunk(const TileArgs& A, int64_t base, i
         else stage_regs<QUAL>(A, mystage, seg_lo, seg_hi, lane, qual_vec);
     }
     const uint32_t qbase = staged ? 2u * seg_lo : 0u;
-    if (LEAN) {
+    if (SLICE) {
+        // the lean record with the read's slot folded into nb (bc_slice::slot_nb)
+        const uint32_t rel4 = (uint32_t)srel * 4u;
+        uint4 v = make_uint4(0u, 0u, 0u, 0u);
+        if (!slow) v = make_uint4(rel4 + T.st[0] * 4u, rel4 + T.en[0] * 4u, bc_slice::slot_nb(lane, msn, srel, T.qd[0], slot_src), 0u);
+        myrec[lane] = v;
+    } else if (LEAN) {
         // one uint4 per read: run 0 of a fast read (the layouts below at NR = 1), nothing of a slow
         // one (an empty range in either layout)
         const uint32_t rel = mpos - (uint32_t)t0, rel4 = rel * 4u;
@@ -582,7 +637,7 @@ __device__ __forceinline__ void process_chunk(const TileArgs& A, int64_t base, i
             myrec[lane * 3 + 2] = make_uint4(rr[3], nb[3], 0u, 0u);
         }
     }
-    if (dma) stage_wait();  // LDS-DMA landed (hipcc does not track it)
+    if (dma || SLICE) stage_wait();  // LDS-DMA landed (hipcc does not track it)
     F = load_fields(A, next_base, next_nr, lane);  // in flight during the walk
     __builtin_amdgcn_wave_barrier();
     const int64_t rbase = base;

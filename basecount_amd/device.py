@@ -193,7 +193,7 @@ class BcPlan(C.Structure):
 
 
 PLAN_KERNELS = ("rc", "solo", "tiles")  # BC_PLAN_*
-INSTANCES = {"auto": 0, "general": 1, "lean": 2}  # BC_INSTANCE_*
+INSTANCES = {"auto": 0, "general": 1, "lean": 2, "slice": 4}  # BC_INSTANCE_* (3 is not a value)
 
 
 class BcLaunchInfo(C.Structure):
@@ -363,7 +363,9 @@ def pileup_launch_info(reads, L: int, shape: str = "auto", tile_waves: int = 0, 
     """bc_pileup_launch_info: the instance a bc_pileup call launches on a context set to (shape,
     tile_waves, instance).  ``reads`` as for pileup_plan; a dict may also give n_cigar_words (the
     routing bound's input; default: one op per read).  Returns kernel, lean (bool), waves_per_tile,
-    block_threads, lds_bytes, blocks and blocks_per_cu of that very kernel (-1 without a device)."""
+    block_threads, lds_bytes, blocks and blocks_per_cu of that very kernel (-1 without a device),
+    and ``slice``: the lean walk's slice instance, which the library reports as lean = 1 with
+    BC_SLICE_LDS_BYTES of LDS (slice_lds_bytes)."""
     if isinstance(reads, dict):
         r = BcReads()
         r.n_reads, r.max_span, r.max_end = int(reads["n_reads"]), int(reads["max_span"]), int(reads["max_end"])
@@ -374,9 +376,15 @@ def pileup_launch_info(reads, L: int, shape: str = "auto", tile_waves: int = 0, 
     p = BcLaunchInfo()
     check(lib().bc_pileup_launch_info(C.byref(r), int(L), SHAPES[shape], int(tile_waves), INSTANCES[instance], int(mbq),
                                       int(k), C.byref(p)))
+    is_slice = bool(p.lean) and p.lds_bytes == slice_lds_bytes(p.block_threads // 64, p.waves_per_tile)
     return {"kernel": PLAN_KERNELS[p.kernel], "lean": bool(p.lean), "waves_per_tile": p.waves_per_tile,
             "block_threads": p.block_threads, "lds_bytes": p.lds_bytes, "blocks": p.blocks,
-            "blocks_per_cu": p.blocks_per_cu}
+            "blocks_per_cu": p.blocks_per_cu, "slice": is_slice}
+
+
+def slice_lds_bytes(waves: int, waves_per_tile: int) -> int:
+    """BC_SLICE_LDS_BYTES (basecount_hip.h): LDS per workgroup of k_pileup's slice instance."""
+    return waves * (1024 + 4096 + 32) + (waves // waves_per_tile) * 1536 + 2048 + 64
 
 
 class DeviceBuffer:
@@ -502,9 +510,10 @@ class Context:
         self.shape_args = (shape, int(tile_waves), int(reads_per_block))
 
     def set_instance(self, instance: str = "auto") -> None:
-        """The tiled k_pileup's instance (bc_ctx_set_instance): "auto" (lean while the batch's
-        bound on multi-run reads is small), "general" or "lean" (A/B runs and tests; both are
-        exact on every batch)."""
+        """The tiled k_pileup's instance (bc_ctx_set_instance): "auto" (the lean walk while the
+        batch's bound on multi-run reads is small, over per-read slices when reads can be longer
+        than a tile), "general", "lean" or "slice" (A/B runs and tests; all are exact on every
+        batch)."""
         check(lib().bc_ctx_set_instance(self.h, INSTANCES[instance]))
 
     def sync(self):

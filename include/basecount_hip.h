@@ -197,33 +197,48 @@ typedef struct bc_plan {
 } bc_plan;
 int bc_pileup_plan(const bc_reads* reads, int64_t ref_len, int shape, int tile_waves, bc_plan* out);
 
-/* The tiled k_pileup has two instances, both exact on every batch:
+/* The tiled k_pileup has three instances, all exact on every batch:
  *   general  the one bc_pileup_plan describes (run tables of up to four runs, deletions, unstaged
  *            chunks; four four-wave workgroups per CU);
  *   lean     only the one-run, ungapped window walk, with every other read (an indel, a skip,
  *            more than 8 ops) walked alone per position; fewer registers and less LDS, so FIVE
  *            four-wave workgroups per CU.  10 % ahead on a batch without such reads, behind
- *            from one such read in 64 on.
+ *            from one such read in 64 on.  A chunk's stage holds
+ *            its 64 reads' whole sequence (up to 94 B per read; longer reads are walked per
+ *            position).
+ *   slice    the lean walk with a stage of 64 slots of 64 B, one per read, each holding only the
+ *            bytes the TILE reads of it: 4 KiB per wave whatever the read length, SIX four-wave
+ *            workgroups per CU.  A read whose leading insertion pushes
+ *            its bases out of its slot is walked per position like the other slow reads.  Built
+ *            without a quality threshold at 32-bit indices.
  * BC_INSTANCE_AUTO therefore takes the lean instance only when (n_cigar_words - n_reads) / 2, an
  * upper bound of the reads with more than one run, is zero (every read has ONE CIGAR op: an
  * ungapped, unclipped batch), and where a lean instance is built (no quality threshold, or 32-bit
  * indices).  n_cigar_words is the CIGAR buffer's count: a bc_reads that is a slice of a larger
  * batch and shares its buffer is judged by the larger batch's count, never by another slice's
  * alone, and keeps the general instance unless every read of the buffer has one op (the bound
- * can be too large for a slice, never too small).  bc_ctx_set_instance forces one for A/B runs and tests
- * (BC_INSTANCE_LEAN where none is built keeps the general one).
+ * can be too large for a slice, never too small).  Where it takes the lean walk it takes the slice
+ * instance when one is built (min_base_quality 0, 32-bit indices) and max_span > 64, a read longer
+ * than a tile: only then is a slice less than the read.  bc_ctx_set_instance forces one for A/B
+ * runs and tests (BC_INSTANCE_LEAN where none is built keeps the general one; BC_INSTANCE_SLICE
+ * where none is built is BC_INSTANCE_LEAN).
  * bc_pileup_plan keeps describing the GENERAL tiled instance whatever bc_pileup launches;
  * bc_pileup_launch_info reports the instance a bc_pileup(ctx, reads, ref_len, mbq, k, ...) call
  * launches on a context set to (shape, tile_waves, instance); like bc_pileup_plan it needs no
  * context, reads no pointer of reads and enqueues nothing:
  *   kernel, waves_per_tile, block_threads, blocks   as in bc_plan
- *   lean           1 the lean instance, 0 the general one (0 for the other kernels)
+ *   lean           1 the lean or the slice instance, 0 the general one (0 for the other kernels);
+ *                  the slice instance is the one with lds_bytes ==
+ *                  BC_SLICE_LDS_BYTES(block_threads / 64, waves_per_tile)
  *   lds_bytes      LDS per workgroup, dynamic + static, of that instance
  *   blocks_per_cu  hipOccupancyMaxActiveBlocksPerMultiprocessor's answer for that very kernel
  *                  (mbq, k and the index width included); -1 when no device is visible          */
 #define BC_INSTANCE_AUTO 0
 #define BC_INSTANCE_GENERAL 1
 #define BC_INSTANCE_LEAN 2
+#define BC_INSTANCE_SLICE 4 /* (3 is not a value) */
+#define BC_SLICE_LDS_BYTES(waves, waves_per_tile) \
+    ((waves) * (1024 + 4096 + 32) + ((waves) / (waves_per_tile)) * 1536 + 2048 + 64)
 int bc_ctx_set_instance(bc_ctx* ctx, int instance);
 typedef struct bc_launch_info {
     int32_t kernel;
