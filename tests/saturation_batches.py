@@ -19,6 +19,7 @@ import functools
 import numpy as np
 
 import oracle as O
+import wide_index as WI
 from basecount_amd import device as D
 from basecount_amd.main import norm_factors
 
@@ -425,10 +426,13 @@ def kernel_for(shape, waves, b):
     return "solo" if (shape, waves) == ("tile", 1) else "pileup"
 
 
-def upload(ctx, b, shape="auto", waves=0, mode=None):
+def upload(ctx, b, shape="auto", waves=0, mode=None, max_end=None):
     """Set the kernel shape, then upload (the upload builds the index of the shape in force);
     mode: k_rc's inputs -- the upload's run records and chunk summaries, the records only, or its
-    own CIGAR decode."""
+    own CIGAR decode.
+    max_end: the launches are to run on ``r.launch``, the batch with max_end raised to it
+    (wide_index.widen: the 64-bit-index instances); without it ``r.launch`` is the batch itself.
+    The device batch is freed through the returned object either way."""
     ctx.set_shape(shape, waves)
     r = D.DeviceReads(ctx, b)
     if mode is not None:
@@ -437,6 +441,7 @@ def upload(ctx, b, shape="auto", waves=0, mode=None):
             r.r.run_chunks = 0
         elif mode == "cigars":
             r.r.read_runs = None
+    r.launch = r.r if max_end is None else WI.widen(r, max_end)
     return r
 
 
@@ -455,8 +460,12 @@ def count_on(ctx, r, L, mbq, ncols):
     return got, bad
 
 
-def pileup_on(ctx, r, L, mbq, k):
+def pileup_on(ctx, r, L, mbq, k, fill=None):
+    """bc_pileup's five outputs and range error; ``fill``: the byte the outputs hold before the call."""
     bufs = [ctx.alloc(max(16, n)) for n in (4 * k * L, 4 * L, 8 * k * L, 8 * L, 8 * L)]
+    if fill is not None:
+        for x in bufs:
+            D.check(D.lib().bc_memset(ctx.h, x.ptr, fill, x.nbytes))
     nf, nf2 = norm_factors(k)
     ctx.pileup(r, L, mbq, k, nf, nf2, *[x.ptr for x in bufs])
     bad = ctx.range_error()
@@ -473,28 +482,32 @@ def same(got, exp, what):
         assert np.array_equal(g, e), (what, name)
 
 
-def check_sorted(ctx, b, L, mbqs, shapes, ks=(5, 6), repeat_last=False):
+def check_sorted(ctx, b, L, mbqs, shapes, ks=(5, 6), repeat_last=False, max_end=None):
     """bc_count (accumulate mode) and bc_pileup of the sorted batch b through every given launch
     shape: the kernel the shape names really ran, the oracle's first out-of-range read, counts /
-    coverage exact and percentages / entropies bit-identical below L."""
+    coverage exact and percentages / entropies bit-identical below L.
+    max_end: the launches run on the batch with max_end raised to it, and every tiled launch must
+    then be a 64-bit-index instance (wide_index.is_wide)."""
     exp = {mbq: expect(b, L, mbq) for mbq in mbqs}
     for shape, waves, mode in shapes:
         kern = kernel_for(shape, waves, b)
         assert mode is None or kern == "rc"
-        r = upload(ctx, b, shape, waves, mode)
+        r = upload(ctx, b, shape, waves, mode, max_end)
         try:
             assert r.r.sorted == 1
             for mbq in mbqs:
                 cnt6, br = exp[mbq]
                 for k in ks:
                     what = (shape, waves, mode, mbq, k)
+                    if max_end is not None and kern != "rc":
+                        assert WI.is_wide(r.launch, L, shape, waves, "auto", mbq, k), what
                     launched(ctx)
-                    got, bad = count_on(ctx, r, L, mbq, k)
+                    got, bad = count_on(ctx, r.launch, L, mbq, k)
                     assert launched(ctx) == {kern}, what
                     assert bad == br, what
                     assert np.array_equal(got, cnt6[:, :k].T.astype(np.int32)), what
                     for _ in range(2 if repeat_last and (mbq, k) == (mbqs[-1], ks[-1]) else 1):
-                        got, bad = pileup_on(ctx, r, L, mbq, k)
+                        got, bad = pileup_on(ctx, r.launch, L, mbq, k, fill=None if max_end is None else 0xFF)
                         assert launched(ctx) == ({"rc", "stats"} if kern == "rc" else {kern}), what
                         assert bad == br, what
                         same(got, expect_stats(cnt6, k), what)
@@ -549,10 +562,11 @@ def check_unsorted(ctx, b, L, mbqs, rpbs=(0, 1, 32768), ks=(5, 6)):
         ctx.set_shape("auto")
 
 
-def check_summaries(ctx, b, L, mbq, k, shapes=(("tile", 1), ("tile_no_solo", 1), ("rc", 0))):
+def check_summaries(ctx, b, L, mbq, k, shapes=(("tile", 1), ("tile_no_solo", 1), ("rc", 0)), max_end=None):
     """bc_pileup_summary, and the summary-only forms (bc_pileup_partials with every output NULL +
     bc_summary_fold; bc_pileup_summary with every output NULL), against bc_pileup followed by
-    bc_summary and against numpy over the oracle's coverage and entropy."""
+    bc_summary and against numpy over the oracle's coverage and entropy.
+    max_end: as for check_sorted (the tiled launches are 64-bit-index instances)."""
     assert L >= 8192  # the sparse summary-only path (bc_sum.hip's own read walk) needs a whole buffer
     cnt6, br = expect(b, L, mbq)
     assert br == -1
@@ -562,29 +576,33 @@ def check_summaries(ctx, b, L, mbq, k, shapes=(("tile", 1), ("tile_no_solo", 1),
     nf, nf2 = norm_factors(k)
     for shape, waves in shapes:
         kern = kernel_for(shape, waves, b)
-        r = upload(ctx, b, shape, waves)
-        bufs = [ctx.alloc(n) for n in (4 * k * L, 4 * L, 8 * L, 8 * L)]
+        r = upload(ctx, b, shape, waves, max_end=max_end)
+        assert max_end is None or kern == "rc" or WI.is_wide(r.launch, L, shape, waves, "auto", mbq, k), shape
+        bufs =[ctx.alloc(n) for n in (4 * k * L, 4 * L, 8 * L, 8 * L)]
         counts, dcov, dent, dsec = [x.ptr for x in bufs]
         work, out = ctx.alloc(D.summary_work_bytes(L)), ctx.alloc(32)
+        if max_end is not None:  # (the wide runs: no output may rely on what the buffer held)
+            for x in bufs:
+                D.check(D.lib().bc_memset(ctx.h, x.ptr, 0xFF, x.nbytes))
         try:
-            ctx.pileup(r, L, mbq, k, nf, nf2, counts, dcov, None, dent, dsec)
+            ctx.pileup(r.launch, L, mbq, k, nf, nf2, counts, dcov, None, dent, dsec)
             ctx.summary(dcov, dent, L, work.ptr, out.ptr)
             base = out.download(np.float64, 4).tolist()
             assert ctx.range_error() == -1
             assert base == want, (shape, "bc_pileup + bc_summary")
             out.zero()
             launched(ctx)
-            ctx.pileup_summary(r, L, mbq, k, nf, nf2, counts, dcov, None, dent, dsec, work.ptr, out.ptr)
+            ctx.pileup_summary(r.launch, L, mbq, k, nf, nf2, counts, dcov, None, dent, dsec, work.ptr, out.ptr)
             assert out.download(np.float64, 4).tolist() == base, (shape, "bc_pileup_summary")
             assert {kern, "summary"} <= launched(ctx) | ({"summary"} if kern == "rc" else set()), shape
             assert np.array_equal(bufs[0].download(np.int32, k * L).reshape(k, L), cnt6[:, :k].T.astype(np.int32))
             out.zero()
-            ctx.pileup_partials(r, L, mbq, k, nf, nf2, None, None, None, None, None, work.ptr)
+            ctx.pileup_partials(r.launch, L, mbq, k, nf, nf2, None, None, None, None, None, work.ptr)
             ctx.summary_fold([L], [work.ptr], [out.ptr])
             assert out.download(np.float64, 4).tolist() == base, (shape, "summary only: partials + fold")
             assert {kern, "summary"} <= launched(ctx), shape
             out.zero()
-            ctx.pileup_summary(r, L, mbq, k, nf, nf2, None, None, None, None, None, work.ptr, out.ptr)
+            ctx.pileup_summary(r.launch, L, mbq, k, nf, nf2, None, None, None, None, None, work.ptr, out.ptr)
             assert out.download(np.float64, 4).tolist() == base, (shape, "summary only: bc_pileup_summary")
             assert ctx.range_error() == -1
         finally:
