@@ -80,6 +80,24 @@ BC_HD RunTable decode_runs(const uint32_t (&w)[kPre], uint32_t cn, int cmax) {
     return T;
 }
 
+// decode_runs' table of a read of ONE CIGAR word (cn == 1), straight from the word: M/=/X of a
+// positive length is the run [0, len) at query delta 0, D/N of a positive length a gap, anything
+// else (I, S, H, P, the unused codes, a zero length) an empty table.
+BC_HD RunTable decode_one_op(uint32_t w0) {
+    RunTable T;
+#pragma unroll
+    for (int i = 0; i < kMaxRuns; ++i) T.st[i] = T.en[i] = 0, T.qd[i] = 0;
+    const uint32_t op = w0 & 15u, len = w0 >> 4;
+    const bool m = mlike(op) && len != 0u, d = dlike(op) && len != 0u;
+    T.en[0] = m ? len : 0u;
+    T.span = (m || d) ? len : 0u;
+    T.qlen = (m || op == 1u) ? len : 0u;
+    T.nrun = m ? 1 : 0;
+    T.gap = d;
+    T.complex = T.span >= 0x1FFFu;
+    return T;
+}
+
 // The 16-byte run record (bc_reads.read_runs, 4 words per read) of a read's first two runs:
 //   x = st0 | en0 << 13 | min(nrun, 7) << 26 | gap << 29 | complex << 30
 //   y = st1 | en1 << 13

@@ -490,7 +490,11 @@ constexpr uint32_t kSpecSlack = 128;  // bytes staged beyond the last read's fir
 // alone (a run that starts at query offset 0 assumed), so a chunk still costs one memory round
 // trip; a read whose decoded run needs a base outside its slot (a leading insertion longer than the
 // slot's slack) is walked as a slow read.  Nothing chunk-wide is reduced: a slice chunk always
-// stages, whatever the reads' length or the order of their sequence.
+// stages, whatever the reads' length or the order of their sequence.  A chunk whose reads all have
+// one CIGAR op (every chunk BC_INSTANCE_AUTO sends here) takes a shorter setup: three pieces per
+// slot, then one CIGAR word per read, loaded AFTER the slices are issued (nothing is outstanding
+// at the wait the compiler puts before the first slice instruction; in the general setup that wait
+// takes the CIGAR loads' round trip before the slices') and decoded directly.
 template <bool QUAL, int K, bool PLANES, bool LEAN = false, bool SLICE = false>
 __device__ __forceinline__ void process_chunk(const TileArgs& A, int64_t base, int nr, ReadFields& F,
                                               int64_t next_base, int next_nr, int lane, int s8, int gb, int64_t t0,
@@ -511,14 +515,26 @@ __device__ __forceinline__ void process_chunk(const TileArgs& A, int64_t base, i
     T.qlen = 0;
 #pragma unroll
     for (int i = 0; i < kMaxRuns; ++i) T.st[i] = T.en[i] = 0, T.qd[i] = 0;
+    // SLICE: a one-op chunk (every read of it has ONE CIGAR op; wave-uniform and known from the
+    // fields, before anything is issued: every chunk of an ungapped batch).  No read of it has a
+    // leading insertion, so its slots need three pieces (bc_slice.h), and its decode is one word's:
+    // one CIGAR load per lane (issued after the slices), no cmax, decode_one_op and covered_one_op
+    // below.  Any other chunk takes the general setup, so the instance stays exact on any batch.
+    bool one = false;
+    if constexpr (SLICE) one = __all(lane >= nr || mcn == 1u);
     // ops to decode: the wave's largest CIGAR (more than kPre -> complex anyway)
-    const int cmax = (int)wave_reduce<true>(mcn < (uint32_t)kPre ? mcn : (uint32_t)kPre);
+    int cmax_of = 1;
     uint32_t w[kPre];
+    uint32_t w0 = 0u;  // a one-op chunk's only word (kept apart from w[]: no other is loaded or zeroed)
+    if (!(SLICE && one)) {
+        cmax_of = (int)wave_reduce<true>(mcn < (uint32_t)kPre ? mcn : (uint32_t)kPre);
 #pragma unroll
-    for (int i = 0; i < kPre; ++i) {
-        w[i] = 0u;
-        if (lane < nr && i < cmax && (uint32_t)i < mcn) w[i] = A.cigar[mcb + i];
+        for (int i = 0; i < kPre; ++i) {
+            w[i] = 0u;
+            if (lane < nr && i < cmax_of && (uint32_t)i < mcn) w[i] = A.cigar[mcb + i];
+        }
     }
+    const int cmax = cmax_of;
     const bool dma = !QUAL && !(BC_ABL(A) & 32);
     uint32_t spec_lo = 0, spec_hi = 0;
     bool spec = false;
@@ -527,12 +543,20 @@ __device__ __forceinline__ void process_chunk(const TileArgs& A, int64_t base, i
         const uint32_t slot_end = (uint32_t)(A.seq_words * 4 < 0xFFFFFFFFll ? A.seq_words * 4 : 0xFFFFFFF0ll);
         const uint32_t slot_src = bc_slice::source_byte(msn, (int32_t)(mpos - (uint32_t)t0));
         const uint32_t piece = (uint32_t)(lane & 3) * (uint32_t)bc_slice::kPieceBytes;
+        // A one-op chunk issues pieces 0-2 of each slot (bc_slice::kOneOpPieces; piece 3's lanes are
+        // off): the slot's stride and the lane deal stay.  The walk's alignbit may still fetch the
+        // first word of bytes [48, 64) as its HIGH operand, for the window that ends the needed
+        // bases: whatever the slot held there before lands on nibbles beyond the run's end, which
+        // tile_mask clears, as it does the stale words of pieces beyond the buffer's end.
+        const bool piece_on = !one || (lane & 3) < bc_slice::kOneOpPieces;
         for (int e = 0; 16 * e < nr; ++e) {  // (uniform) 16 reads' slots per instruction
             const int r = 16 * e + (lane >> 2);
             const uint32_t src = (uint32_t)__shfl((int)slot_src, r) + piece;
-            if (r < nr && src < slot_end)  // bc_slice::piece_issued
+            if (r < nr && src < slot_end && piece_on)  // bc_slice::piece_issued
                 __builtin_amdgcn_global_load_lds((gbl_void_t*)(A.seq + src), (lds_void_t*)(mystage + 1024 * e), 16, 0, 0);
         }
+        // the one-op chunk's CIGAR word, in flight with the slices
+        if (one && lane < nr) w0 = A.cigar[mcb];
     } else if (dma && !(BC_ABL(A) & 512)) {
         const uint32_t buf_end = (uint32_t)(A.seq_words * 4 < 0xFFFFFFFFll ? A.seq_words * 4 : 0xFFFFFFF0ll);
         spec_lo = (rdl(msn, 0) >> 1) & ~15u;
@@ -541,7 +565,9 @@ __device__ __forceinline__ void process_chunk(const TileArgs& A, int64_t base, i
         spec = spec_hi > spec_lo && spec_hi - spec_lo <= (uint32_t)STG;
         if (spec) stage_dma<64>(mystage, A.seq + spec_lo, spec_hi - spec_lo, lane);
     }
-    if (lane < nr) T = LEAN ? decode_runs<1>(w, mcn, cmax) : decode_runs(w, mcn, cmax);
+    // (a one-op chunk's padding lanes hold a zero word: the empty table)
+    if (SLICE && one) T = decode_one_op(w0);
+    else if (lane < nr) T = LEAN ? decode_runs<1>(w, mcn, cmax) : decode_runs(w, mcn, cmax);
     // LEAN: no chunk-wide property is reduced; `slow` is the lane's own read
     // SLICE: the slot's source byte again (not kept in a register through the decode), and whether
     // the slot holds what the decoded run needs
@@ -554,7 +580,8 @@ __device__ __forceinline__ void process_chunk(const TileArgs& A, int64_t base, i
         srel = (int32_t)(mpos - (uint32_t)t0);
         slot_src = bc_slice::source_byte(sn2, srel);
         const uint32_t slot_end = (uint32_t)(A.seq_words * 4 < 0xFFFFFFFFll ? A.seq_words * 4 : 0xFFFFFFF0ll);
-        miss = !bc_slice::covered(msn, srel, T.st[0], T.en[0], T.qd[0], slot_src, slot_end);
+        if (one) miss = !bc_slice::covered_one_op(msn, srel, T.en[0], slot_src, slot_end);
+        else miss = !bc_slice::covered(msn, srel, T.st[0], T.en[0], T.qd[0], slot_src, slot_end);
     }
     const bool slow = LEAN && (T.complex || T.gap || T.nrun > 1 || (SLICE && miss));
     const bool cx = LEAN ? false : __any(T.complex);
