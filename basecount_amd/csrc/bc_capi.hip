@@ -12,6 +12,7 @@
 
 #include "bc_cohort.h"
 #include "bc_internal.h"
+#include "bc_ops_plan.h"
 
 namespace {
 
@@ -65,7 +66,9 @@ struct DeviceGuard {
 hipError_t launch_chunked(bc_ctx* c, const bc_reads& r, int64_t L, uint32_t mbq, int k, int32_t* counts) {
     if (c->shape == BC_SHAPE_OPS) {
         Timed tm(c, BC_K_COUNT);
-        return bc::launch_ops(c->stream, r, L, mbq, k, counts, c->d_err, c->reads_per_block);
+        struct bc_ops_plan plan;
+        bc::ops_plan(r, L, c->reads_per_block, c->ops_passes, plan);
+        return bc::launch_ops(c->stream, r, L, mbq, k, counts, c->d_err, plan);
     }
     Timed tm(c, BC_K_RC);
     return bc::launch_rc(c->stream, r, L, mbq, k, counts, c->d_err);
@@ -863,6 +866,22 @@ int bc_pileup_plan(const bc_reads* r, int64_t ref_len, int shape, int tile_waves
     if (tile_waves != 0 && tile_waves != 1 && tile_waves != 2 && tile_waves != 4 && tile_waves != 8)
         return fail(BC_E_ARG, "tile_waves must be 0, 1, 2, 4 or 8");
     bc::pileup_plan(*r, ref_len, shape, tile_waves, *out);
+    return BC_OK;
+}
+
+int bc_ops_plan(const bc_reads* r, int64_t ref_len, int rpb, int passes, struct bc_ops_plan* out) {
+    if (!r || !out) return fail(BC_E_ARG, "NULL argument");
+    if (r->n_reads < 0 || ref_len < 0) return fail(BC_E_ARG, "bc_ops_plan: n_reads or ref_len < 0");
+    if (rpb < 0) return fail(BC_E_ARG, "reads_per_block must be >= 0");
+    if (passes < 0 || passes > BC_OPS_PASSES_MAX) return fail(BC_E_ARG, "passes must be 0..BC_OPS_PASSES_MAX");
+    bc::ops_plan(*r, ref_len, rpb, passes, *out);
+    return BC_OK;
+}
+
+int bc_ctx_set_ops_passes(bc_ctx* c, int passes) {
+    if (!c) return fail(BC_E_ARG, "ctx is NULL");
+    if (passes < 0 || passes > BC_OPS_PASSES_MAX) return fail(BC_E_ARG, "passes must be 0..BC_OPS_PASSES_MAX");
+    c->ops_passes = passes;
     return BC_OK;
 }
 

@@ -40,6 +40,7 @@ struct bc_ctx {
     int tile_waves = 0;
     int reads_per_block = 0;
     int instance = BC_INSTANCE_AUTO;  // k_pileup's instance (bc_ctx_set_instance)
+    int ops_passes = 0;               // k_ops' window passes (bc_ctx_set_ops_passes); 0 = from the batch
 };
 
 // Diagnostic work-skipping switches (BC_ABLATE) exist only in -DBC_DIAG builds
@@ -121,10 +122,9 @@ hipError_t launch_sum_sparse(hipStream_t s, const bc_reads& r, int64_t L, uint32
 hipError_t launch_rc(hipStream_t s, const bc_reads& r, int64_t L, uint32_t mbq, int ncols, int32_t* counts,
                      unsigned long long* d_err);
 // k_ops (bc_ops.hip, BC_SHAPE_OPS): launch_rc's contract for batches of many-op reads, sorted or
-// not; reads_per_block 0 = from the batch (ops_reads_per_block), else 1..32768
-int ops_reads_per_block(const bc_reads& r, int64_t L, int forced);
+// not; plan: ops_plan's (bc_ops_plan.h) for the batch, ref_len and the context's overrides
 hipError_t launch_ops(hipStream_t s, const bc_reads& r, int64_t L, uint32_t mbq, int ncols, int32_t* counts,
-                      unsigned long long* d_err, int reads_per_block);
+                      unsigned long long* d_err, const struct bc_ops_plan& plan);
 // bc_pileup / bc_count choose the read-chunked k_rc over the tiled k_pileup when a tile would
 // walk at least this many reads (deep batches; bc_ctx_set_shape overrides)
 constexpr double kRcMinReadsPerTile = 2048.0;

@@ -193,6 +193,12 @@ class BcPlan(C.Structure):
 
 
 PLAN_KERNELS = ("rc", "solo", "tiles")  # BC_PLAN_*
+OPS_PASSES_MAX = 16  # BC_OPS_PASSES_MAX
+
+
+class BcOpsPlan(C.Structure):
+    _fields_ = [("reads_per_block", C.c_int32), ("window", C.c_int32), ("passes_max", C.c_int32),
+                ("reserved", C.c_int32), ("blocks", C.c_int64)]
 INSTANCES = {"auto": 0, "general": 1, "lean": 2, "slice": 4}  # BC_INSTANCE_* (3 is not a value)
 
 
@@ -233,6 +239,8 @@ def lib() -> C.CDLL:
         "bc_ctx_set_shape": ([vp, C.c_int, C.c_int, C.c_int], C.c_int),
         "bc_pileup_plan": ([C.POINTER(BcReads), i64, C.c_int, C.c_int, C.POINTER(BcPlan)], C.c_int),
         "bc_ctx_set_instance": ([vp, C.c_int], C.c_int),
+        "bc_ops_plan": ([C.POINTER(BcReads), i64, C.c_int, C.c_int, C.POINTER(BcOpsPlan)], C.c_int),
+        "bc_ctx_set_ops_passes": ([vp, C.c_int], C.c_int),
         "bc_pileup_launch_info": ([C.POINTER(BcReads), i64, C.c_int, C.c_int, C.c_int, u32, C.c_int,
                                    C.POINTER(BcLaunchInfo)], C.c_int),
         "bc_malloc": ([vp, C.c_size_t, C.POINTER(vp)], C.c_int),
@@ -356,6 +364,30 @@ def pileup_plan(reads, L: int, shape: str = "auto", tile_waves: int = 0) -> dict
     return {"kernel": PLAN_KERNELS[p.kernel], "waves_per_tile": p.waves_per_tile, "block_threads": p.block_threads,
             "lds_bytes": p.lds_bytes, "blocks": p.blocks, "blocks_per_cu": p.blocks_per_cu,
             "tiles_per_wave": p.tiles_per_wave, "reads_per_tile": p.reads_per_tile}
+
+
+def ops_plan(reads, L: int, reads_per_block: int = 0, passes: int = 0) -> dict:
+    """bc_ops_plan: what the "ops" shape launches for a batch on a reference of L positions.
+    ``reads``: a DeviceReads, a BcReads, or a dict with n_reads, sorted, max_span, max_end and
+    seq_bytes (only the header is read, never a pointer).  reads_per_block 0 = from the batch, else
+    forced (at most 32768); passes 0 = from the batch, 1 = the single window, 2..OPS_PASSES_MAX =
+    that many window passes at most.  Returns reads_per_block, window (4096 positions; 0 for an
+    unsorted batch, which has none), passes_max (1: the single-pass kernel; more: a workgroup runs
+    up to that many passes over consecutive windows from its first read's start and ends when none
+    of its reads reaches further) and blocks.  A sorted batch whose typical read, min(2 x seq_bytes
+    / n_reads, max_span), is at most 2048 positions gets passes_max 1 unless passes forces more;
+    longer reads get the reads that start within one window per block (at least 4) and the passes
+    they can reach."""
+    if isinstance(reads, dict):
+        r = BcReads()
+        r.n_reads, r.sorted = int(reads["n_reads"]), int(reads.get("sorted", 1))
+        r.max_span, r.max_end, r.seq_bytes = int(reads["max_span"]), int(reads["max_end"]), int(reads["seq_bytes"])
+        r.seq_layout = BC_SEQ_EVENT
+    else:
+        r = reads.r if isinstance(reads, DeviceReads) else reads
+    p = BcOpsPlan()
+    check(lib().bc_ops_plan(C.byref(r), int(L), int(reads_per_block), int(passes), C.byref(p)))
+    return {"reads_per_block": p.reads_per_block, "window": p.window, "passes_max": p.passes_max, "blocks": p.blocks}
 
 
 def pileup_launch_info(reads, L: int, shape: str = "auto", tile_waves: int = 0, instance: str = "auto",
@@ -515,6 +547,12 @@ class Context:
         than a tile), "general", "lean" or "slice" (A/B runs and tests; all are exact on every
         batch)."""
         check(lib().bc_ctx_set_instance(self.h, INSTANCES[instance]))
+
+    def set_ops_passes(self, passes: int = 0) -> None:
+        """The window passes of the "ops" shape's kernel (bc_ctx_set_ops_passes): 0 (ops_plan
+        decides from the batch), 1 (the single window and its launch) or 2..OPS_PASSES_MAX (that
+        many at most, on any sorted batch).  A/B runs and tests; every setting counts the same."""
+        check(lib().bc_ctx_set_ops_passes(self.h, int(passes)))
 
     def sync(self):
         check(lib().bc_sync(self.h))

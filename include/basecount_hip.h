@@ -143,8 +143,9 @@ int bc_ctx_release_scratch(bc_ctx* ctx);
  *                         picked by BC_SHAPE_AUTO.  bc_count under it also takes unsorted
  *                         BC_SEQ_EVENT batches (any sequence alignment); BC_SEQ_BAM batches keep
  *                         k_count.  Reads no index: BC_INDEX_AUTO builds none, reads_per_block
- *                         (0 = from the batch) is the reads per k_ops workgroup.  Timed under
- *                         BC_K_COUNT.
+ *                         (0 = from the batch) is the reads per k_ops workgroup.  Reads longer
+ *                         than its LDS window are counted over window passes (bc_ops_plan
+ *                         below).  Timed under BC_K_COUNT.
  * tile_waves: 0 = from the depth, else 1, 2, 4 or 8 waves per 64-position tile (BC_E_ARG
  * otherwise).  reads_per_block: 0 = automatic, else 1..32768 reads per k_count workgroup
  * (unsorted batches).                                                                          */
@@ -154,6 +155,39 @@ int bc_ctx_release_scratch(bc_ctx* ctx);
 #define BC_SHAPE_TILE_NO_SOLO 3
 #define BC_SHAPE_OPS 4
 int bc_ctx_set_shape(bc_ctx* ctx, int shape, int tile_waves, int reads_per_block);
+
+/* k_ops' launch for a batch (BC_SHAPE_OPS), from the batch's header alone: n_reads, sorted,
+ * max_span, max_end and seq_bytes are read, no pointer is dereferenced, nothing is enqueued and
+ * no context is needed.  A workgroup takes reads_per_block consecutive reads.  For a sorted batch
+ * it counts into an LDS window of `window` = 4,096 positions and runs up to passes_max passes:
+ * pass p owns the positions [first read's start + p x window, + (p + 1) x window), every counted
+ * event is examined in exactly the pass that owns its position (events at or beyond the end of
+ * the last pass's window in the last pass, as global atomics), the window is cleared before and
+ * flushed after every pass, and the passes end as soon as no read of the workgroup reaches
+ * further.  The counts are those of the single window, bit for bit.
+ *   typical read = min(2 x seq_bytes / n_reads, max_span) <= 2,048, or an unsorted batch:
+ *       reads_per_block as the single-window rule gives it (DESIGN.md section 3 "k_ops"),
+ *       passes_max 1: the single-pass kernel; an unsorted batch has window 0
+ *   longer reads: reads_per_block the reads that start within one window, 4,096 x n_reads /
+ *       max(ref_len, max_end), at least 4 (a read per wave) and at most n_reads / 2,048 clamped to
+ *       [32, 8,192]; passes_max what the workgroup's reads can reach, (reads_per_block x
+ *       max(ref_len, max_end) / n_reads + max_span) / 4,096 + 1, at least 2 and at most
+ *       BC_OPS_PASSES_MAX (that cap when max_span is 0)
+ * reads_per_block: 0 = from the batch, else forced (at most 32,768: a 16-bit half of the window
+ * counts one workgroup's reads at one position).  passes: 0 = from the batch, 1 = the single
+ * window and its own reads_per_block, 2..BC_OPS_PASSES_MAX = that many at most, for any sorted
+ * batch, with the reads_per_block of passes = 0.  `blocks` is the launch's workgroups.
+ * bc_ctx_set_ops_passes sets `passes` for the context's launches (A/B runs and tests, as
+ * bc_ctx_set_instance; BC_E_ARG outside 0..BC_OPS_PASSES_MAX); reads_per_block is
+ * bc_ctx_set_shape's.  Measured in DESIGN.md section 3 "k_ops".                                */
+#define BC_OPS_PASSES_MAX 16
+struct bc_ops_plan { /* (the call has the tag's name, as stat has: no typedef) */
+    int32_t reads_per_block, window, passes_max;
+    int32_t reserved;
+    int64_t blocks;
+};
+int bc_ops_plan(const bc_reads* reads, int64_t ref_len, int reads_per_block, int passes, struct bc_ops_plan* out);
+int bc_ctx_set_ops_passes(bc_ctx* ctx, int passes);
 
 /* What bc_pileup launches for a coordinate-sorted BC_SEQ_EVENT batch on a reference of ref_len
  * positions under (shape, tile_waves), from the batch's header alone: n_reads, max_span and
