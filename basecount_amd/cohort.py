@@ -13,6 +13,8 @@ the ``basecount`` command do.
     python -m basecount_amd.cohort [every flag of basecount] --out-dir DIR BAM [BAM ...]
 
 writes DIR/X.tsv for input X.bam: the bytes ``python -m basecount_amd X.bam <flags>`` prints.
+With ``--bgzf`` (what BASECOUNT_BGZF=1 sets, for the call) the per-position outputs are written as
+BGZF, DIR/X.tsv.gz: the bytes that command prints under the switch.
 """
 from __future__ import annotations
 
@@ -158,16 +160,16 @@ def plan_cohort(facts, cap: int | None = None, budget: int | None = None, want_q
     return [u[1] for u in units if u[0] == "group"], [(u[1], u[2]) for u in units if u[0] == "single"]
 
 
-def output_names(bams, out_dir: str) -> list:
-    """DIR/X.tsv for X.bam (the extension dropped, whatever it is); duplicate basenames are refused
-    before any work starts."""
+def output_names(bams, out_dir: str, ext: str = ".tsv") -> list:
+    """DIR/X.tsv for X.bam (the extension dropped, whatever it is; ``ext``: ".tsv.gz" under --bgzf);
+    duplicate basenames are refused before any work starts."""
     seen, out = {}, []
     for b in bams:
         stem = os.path.splitext(os.path.basename(os.fspath(b)))[0]
         if stem in seen:
-            raise ValueError(f"duplicate basename {stem!r}: {seen[stem]} and {b} would both write {stem}.tsv")
+            raise ValueError(f"duplicate basename {stem!r}: {seen[stem]} and {b} would both write {stem}{ext}")
         seen[stem] = b
-        out.append(os.path.join(out_dir, stem + ".tsv"))
+        out.append(os.path.join(out_dir, stem + ext))
     return out
 
 
@@ -471,7 +473,8 @@ def get_basecounts_many(bams, references=None, min_base_quality=0, min_mapping_q
                         r, nr = by_tid[t], int(d.nreads[t])
                         if text:
                             if isinstance(r, M.RefData):  # not covered or declined: the host formatter
-                                r = fmt.rows_text(ref, r.counts[:k], r.pc, r.ent, r.sec, dp, long_format)
+                                r = M.bgzf_text(fmt.rows_text(ref, r.counts[:k], r.pc, r.ent, r.sec, dp, long_format),
+                                                k if long_format else 1)
                             out[ref] = {"text": r, "num_reads": nr}
                         elif mode == "rows":
                             out[ref] = {"rows": M.Rows(ref, r, long_format), "num_reads": nr}
@@ -521,6 +524,8 @@ def build_parser():
     parser.add_argument("--out-dir", required=True, metavar="DIR",
                         help="Directory the outputs are written to: DIR/X.tsv for input X.bam")
     parser.add_argument("--bam-list", default=None, metavar="FILE", help="A file of BAM paths, one per line")
+    parser.add_argument("--bgzf", action="store_true",
+                        help="Write the per-position outputs as BGZF: DIR/X.tsv.gz (summaries stay plain text)")
     return parser
 
 
@@ -541,9 +546,23 @@ def _stdout_to(path):
 
 def run(argv=None) -> int:
     """The command: returns the exit status (1 if any file failed)."""
+    args = build_parser().parse_args(argv)
+    if not args.bgzf:
+        return _run(args)
+    before = os.environ.get("BASECOUNT_BGZF")
+    os.environ["BASECOUNT_BGZF"] = "1"  # what the switch sets, for the duration of the call
+    try:
+        return _run(args)
+    finally:
+        if before is None:
+            del os.environ["BASECOUNT_BGZF"]
+        else:
+            os.environ["BASECOUNT_BGZF"] = before
+
+
+def _run(args) -> int:
     from . import dist
 
-    args = build_parser().parse_args(argv)
     if dist.env()[0] > 1:
         print("basecount cohort: WORLD_SIZE > 1 is not supported (files are not sharded over ranks)", file=sys.stderr)
         return 2
@@ -561,7 +580,8 @@ def run(argv=None) -> int:
         print("basecount cohort: no BAM file given", file=sys.stderr)
         return 2
     try:
-        outs = dict(zip(bams, output_names(bams, args.out_dir)))
+        gz = (not args.summarise) and bed is None and M.device_bgzf_on()
+        outs = dict(zip(bams, output_names(bams, args.out_dir, ".tsv.gz" if gz else ".tsv")))
     except ValueError as e:
         print(f"basecount cohort: {e}", file=sys.stderr)
         return 2
@@ -600,7 +620,14 @@ def run(argv=None) -> int:
         """A fast-path file's output, written as soon as its group is done."""
         t0 = time.perf_counter()
         with _stdout_to(outs[path]):
-            if rows:
+            if rows and M.device_bgzf_on():
+                from . import bgzf
+
+                with bgzf.Writer() as w:
+                    w.write(("\t".join(M._columns(args.show_n_bases, args.long_format)) + "\n").encode())
+                    for ref, v in r.items():
+                        w.write_blocks(v["text"])
+            elif rows:
                 print("\t".join(M._columns(args.show_n_bases, args.long_format)))
                 for ref, v in r.items():
                     if text:

@@ -841,6 +841,50 @@ int bc_fmt_rows(bc_ctx* c, const bc_fmt_args* a, void* d_work, size_t work_bytes
     return BC_OK;
 }
 
+// ---- BGZF deflate on the device (bc_deflate.hip) ----
+namespace {
+const char* dfl_size_error(int64_t text_cap, int64_t n_spans) {
+    if (text_cap < 0 || n_spans < 0) return "negative text_cap or n_spans";
+    if (text_cap >= (1ll << 40)) return "text_cap must be below 2^40";
+    if (n_spans < 1) return "n_spans must be at least 1";
+    if (n_spans > 0x7FFFFFFFll) return "n_spans must be below 2^31";
+    return nullptr;
+}
+}  // namespace
+
+int bc_bgzf_deflate_bytes(int64_t text_cap, int64_t n_spans, size_t* work_bytes, size_t* out_small_bytes) {
+    if (!work_bytes || !out_small_bytes) return fail(BC_E_ARG, "bc_bgzf_deflate_bytes: NULL pointer");
+    if (const char* m = dfl_size_error(text_cap, n_spans)) return fail(BC_E_ARG, std::string("bc_bgzf_deflate_bytes: ") + m);
+    *work_bytes = bc::deflate_work_bytes(text_cap, n_spans);
+    *out_small_bytes = 64u + 8u * ((size_t)n_spans + 1u);
+    return BC_OK;
+}
+
+int bc_bgzf_deflate(bc_ctx* c, const uint8_t* d_text, int64_t text_cap, const int64_t* d_span_off, int64_t n_spans,
+                    const int32_t* d_gate, void* d_work, size_t work_bytes, void* d_out_small, uint8_t* d_comp,
+                    int64_t comp_cap) {
+    if (!c) return fail(BC_E_ARG, "ctx is NULL");
+    if (!d_text || !d_span_off || !d_work || !d_out_small || !d_comp) return fail(BC_E_ARG, "bc_bgzf_deflate: NULL pointer");
+    if (const char* m = dfl_size_error(text_cap, n_spans)) return fail(BC_E_ARG, std::string("bc_bgzf_deflate: ") + m);
+    if (comp_cap < 0) return fail(BC_E_ARG, "bc_bgzf_deflate: negative comp_cap");
+    if (work_bytes < bc::deflate_work_bytes(text_cap, n_spans))
+        return fail(BC_E_ARG, "bc_bgzf_deflate: d_work smaller than bc_bgzf_deflate_bytes");
+    if ((uintptr_t)d_work & 15u) return fail(BC_E_ARG, "bc_bgzf_deflate: d_work must be 16-byte aligned");
+    if (((uintptr_t)d_span_off | (uintptr_t)d_out_small) & 7u)
+        return fail(BC_E_ARG, "bc_bgzf_deflate: d_span_off and d_out_small must be 8-byte aligned");
+    if ((uintptr_t)d_gate & 3u) return fail(BC_E_ARG, "bc_bgzf_deflate: d_gate must be 4-byte aligned");
+    DeviceGuard g(c->device);
+    HIP_TRY(bc::launch_deflate(c->stream, d_text, text_cap, d_span_off, n_spans, d_gate, d_work, d_out_small, d_comp, comp_cap));
+    return BC_OK;
+}
+
+int bc_bgzf_deflate_host(const uint8_t* h_text, const int64_t* h_span_off, int64_t n_spans, uint8_t* h_comp,
+                         int64_t comp_cap, int64_t* span_coff, int64_t* total, int nthreads) {
+    if (!h_text || !h_span_off || !h_comp || !span_coff || !total) return fail(BC_E_ARG, "bc_bgzf_deflate_host: NULL pointer");
+    if (n_spans < 1 || n_spans > 0x7FFFFFFFll || comp_cap < 0) return fail(BC_E_ARG, "bc_bgzf_deflate_host: n_spans < 1 or negative comp_cap");
+    return bc::deflate_host(h_text, h_span_off, n_spans, h_comp, comp_cap, span_coff, total, nthreads);
+}
+
 int bc_ctx_stream(bc_ctx* c, void** s) {
     if (!c || !s) return fail(BC_E_ARG, "NULL argument");
     *s = (void*)c->stream;

@@ -233,6 +233,13 @@ size_t select_bytes(int64_t n, int64_t n_refs);
 hipError_t launch_select(hipStream_t s, const bc_bam_arrays& rec, int64_t n, int64_t min_mapq, const uint8_t* ref_sel,
                          const int64_t* ref_len, int32_t n_refs, void* work, const bc_sel_arrays& out);
 
+// ---- BGZF deflate (bc_deflate.hip over bc_deflate.h): the argument limits are the caller's check ----
+size_t deflate_work_bytes(int64_t text_cap, int64_t n_spans);
+hipError_t launch_deflate(hipStream_t s, const uint8_t* text, int64_t text_cap, const int64_t* span_off, int64_t n_spans,
+                          const int32_t* gate, void* work, void* out_small, uint8_t* comp, int64_t comp_cap);
+int deflate_host(const uint8_t* text, const int64_t* span_off, int64_t n_spans, uint8_t* comp, int64_t comp_cap,
+                 int64_t* span_coff, int64_t* total, int nthreads);
+
 // ---- row formatting (bc_fmt.hip over bc_fmt.h): the argument limits are the caller's check ----
 size_t fmt_work_bytes(int64_t n);
 hipError_t launch_fmt_rows(hipStream_t s, const bc_fmt_args& args, void* work, void* out, uint8_t* text,

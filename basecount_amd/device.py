@@ -173,6 +173,39 @@ def fmt_table(segs) -> tuple:
     return tab, np.frombuffer(b"".join(blob) + b"\0", np.uint8)
 
 
+DFL_HEADER_DTYPE = np.dtype([("status", "<i4"), ("n_stored", "<i4"), ("n_blocks", "<i8"), ("total_bytes", "<i8"),
+                             ("text_bytes", "<i8"), ("reserved", "<i8", (4,))])  # bc_dfl_header, 64 bytes
+DFL_STATUS = ("ok", "too_small", "gated", "offsets")  # BC_DFL_*
+DFL_OK, DFL_TOO_SMALL, DFL_GATED, DFL_OFFSETS = 0, 1, 2, 3
+DFL_BLOCK = 65280  # input bytes of a BGZF block
+
+
+def bgzf_deflate_bytes(text_cap: int, n_spans: int) -> tuple:
+    """bc_bgzf_deflate_bytes: (bytes of the work buffer, bytes of the header + span_coff)."""
+    w, o = C.c_size_t(0), C.c_size_t(0)
+    check(lib().bc_bgzf_deflate_bytes(int(text_cap), int(n_spans), C.byref(w), C.byref(o)))
+    return int(w.value), int(o.value)
+
+
+def bgzf_deflate_host(text, span_off=None, nthreads: int = 16) -> tuple:
+    """bc_bgzf_deflate_host: (compressed bytes as uint8, span_coff) of a bytes-like text cut at span_off
+    (default: one span), the bytes bc_bgzf_deflate writes; no device is touched, no EOF block added."""
+    t = np.frombuffer(text, np.uint8) if not isinstance(text, np.ndarray) else np.ascontiguousarray(text, np.uint8)
+    off = np.ascontiguousarray([0, t.size] if span_off is None else span_off, np.int64)
+    n = off.size - 1
+    src = t if t.size else np.zeros(1, np.uint8)
+    # a fixed-code block is below its input + 5 + 26 bytes (the stored fallback), a span adds a cut
+    cap = int(t.size + 31 * (t.size // DFL_BLOCK + n) + 64)
+    comp, coff, total = np.empty(cap, np.uint8), np.zeros(n + 1, np.int64), C.c_int64(0)
+    rc = lib().bc_bgzf_deflate_host(src.ctypes.data, off.ctypes.data, n, comp.ctypes.data, cap, coff.ctypes.data,
+                                    C.byref(total), int(nthreads))
+    if rc < 0:
+        check(rc)
+    if rc != DFL_OK:
+        raise ValueError("bc_bgzf_deflate_host: " + DFL_STATUS[rc])
+    return comp[:total.value], coff
+
+
 BAM_STATUS = ("ok", "partial_len", "partial", "short", "neg_lseq", "fields", "too_large", "repairs", "internal")  # BC_BAM_*
 
 
@@ -309,6 +342,10 @@ def lib() -> C.CDLL:
         # row formatting on the device (bc_fmt.hip)
         "bc_fmt_rows_bytes": ([i64, i64, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)], C.c_int),
         "bc_fmt_rows": ([vp, C.POINTER(BcFmtArgs), vp, C.c_size_t, vp, vp, i64], C.c_int),
+        # BGZF deflate on the device (bc_deflate.hip)
+        "bc_bgzf_deflate_bytes": ([i64, i64, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)], C.c_int),
+        "bc_bgzf_deflate": ([vp, vp, i64, vp, i64, vp, vp, C.c_size_t, vp, vp, i64], C.c_int),
+        "bc_bgzf_deflate_host": ([vp, vp, i64, vp, i64, vp, C.POINTER(i64), C.c_int], C.c_int),
         # multi-GPU (bc_comm.hip)
         "bc_comm_unique_id": ([vp], C.c_int),
         "bc_comm_init": ([vp, vp, C.c_int, C.c_int, C.POINTER(vp)], C.c_int),
@@ -716,6 +753,14 @@ class Context:
         mmq = max(min(int(min_mapq), 1 << 40), -(1 << 40))
         check(lib().bc_bam_select(self.h, C.byref(rec), int(n), mmq, d_ref_sel, d_ref_len, int(n_refs), d_work,
                                   int(work_bytes), C.byref(out)))
+
+    def bgzf_deflate(self, d_text: int, text_cap: int, d_span_off: int, n_spans: int, d_gate, d_work: int,
+                     work_bytes: int, d_out_small: int, d_comp: int, comp_cap: int) -> None:
+        """bc_bgzf_deflate: spans of device text into BGZF blocks in d_comp, stream-ordered (capturable,
+        no allocation).  d_out_small: the 64-byte header (DFL_HEADER_DTYPE) and span_coff[n_spans + 1];
+        d_gate: None or a device int32 that, non-zero, turns the call into a header write (DFL_GATED)."""
+        check(lib().bc_bgzf_deflate(self.h, d_text, int(text_cap), d_span_off, int(n_spans), d_gate, d_work,
+                                    int(work_bytes), d_out_small, d_comp, int(comp_cap)))
 
     def fmt_rows(self, args: BcFmtArgs, d_work: int, work_bytes: int, d_out: int, d_text: int, text_cap: int) -> None:
         """bc_fmt_rows: the TSV rows of device-resident outputs into d_text, stream-ordered (capturable,

@@ -100,7 +100,17 @@ def device_select_on() -> bool:
 # kernels left them, and the host downloads a header, the segment offsets and the text instead of
 # five arrays per reference.  Independent of the input switches; unsharded rows runs only.
 def device_format_on() -> bool:
-    return os.environ.get("BASECOUNT_DEVICE_FORMAT") not in (None, "", "0")
+    return os.environ.get("BASECOUNT_DEVICE_FORMAT") not in (None, "", "0") or device_bgzf_on()
+
+
+# BASECOUNT_BGZF=1: the rows leave as BGZF ("Device deflate"): bc_bgzf_deflate compresses
+# the formatter's text where bc_fmt_rows left it, on its segment offsets and gated on its status, and
+# the host downloads whole compressed blocks instead of the text.  What the device formatter does not
+# cover (and the column line, and a sharded run's rows) is compressed by the kernels' host twin: the
+# file is the same bytes whichever side compressed a reference.  Implies device formatting; the
+# summary shapes stay plain text.
+def device_bgzf_on() -> bool:
+    return os.environ.get("BASECOUNT_BGZF") not in (None, "", "0")
 
 
 _DECODE_MS = {"fills": 0, "upload_ms": 0.0, "inflate_ms": 0.0, "index_ms": 0.0, "fill_ms": 0.0, "download_ms": 0.0,
@@ -853,6 +863,26 @@ def _reads_inside(pos, span, ref_beg, lengths_t) -> np.ndarray:
 FORMAT_SLICE = 1 << 22  # array positions of one bc_fmt_rows call: the text buffer stays bounded
 _FORMAT_MS = {"calls": 0, "device_ms": 0.0, "download_ms": 0.0, "text_bytes": 0, "retries": 0}
 FORMAT_TIMING = False  # event pairs around bc_fmt_rows without BASECOUNT_HIP_TIMING (scripts/format_bench.py)
+_BGZF_MS = {"calls": 0, "device_ms": 0.0, "download_ms": 0.0, "text_bytes": 0, "comp_bytes": 0, "blocks": 0,
+            "stored": 0, "retries": 0}
+
+
+def bgzf_text(text, rows_per_pos: int = 1):
+    """A reference's rows as they leave: under BASECOUNT_BGZF the text's BGZF blocks by the kernels'
+    host twin, otherwise the text itself.  The twin cuts where the device does: a reference longer
+    than FORMAT_SLICE positions is one span per slice (_DeviceFormatter.reference), so the blocks are
+    the bytes the device writes for the same text."""
+    if not device_bgzf_on():
+        return text
+    if not len(text):
+        return b""
+    arr = np.frombuffer(text, np.uint8)
+    off, per = [0], FORMAT_SLICE * int(rows_per_pos)
+    if arr.size > per:  # (a row is more than a byte)
+        ends = np.flatnonzero(arr == 10)
+        off += [int(ends[r - 1]) + 1 for r in range(per, ends.size, per)]
+    off.append(arr.size)
+    return memoryview(D.bgzf_deflate_host(arr, off)[0])
 
 
 class _DeviceFormatter:
@@ -866,6 +896,8 @@ class _DeviceFormatter:
         self.ctx, self.scratch, self.k, self.dp, self.long = ctx, scratch, int(k), int(dp), bool(long_format)
         self.name, self.names = None, None
         self.per_pos = 0.0  # text bytes per position seen so far (the next buffer's estimate)
+        self.bgzf = device_bgzf_on()  # the text stays in HBM; whole BGZF blocks come back instead
+        self.ratio, self.seen = 0.5, 0.0  # compressed / text bytes (the compressed buffer's estimate)
         self.timing = bool(os.environ.get("BASECOUNT_HIP_TIMING")) or FORMAT_TIMING
         self.plan = PLAN["format"]  # the call's routing: the declined references are named here
 
@@ -899,11 +931,20 @@ class _DeviceFormatter:
         cap = self._estimate(segs, n)
         for attempt in (0, 1):
             text = sc.get("fmt_text", cap)
+            if self.bgzf:  # behind the formatter, on its seg_off and gated on its status: no round trip
+                dwb, dob = D.bgzf_deflate_bytes(text.nbytes, len(segs))
+                ccap = int(text.nbytes * min(1.0, self.ratio * 1.15)) + 65536
+                dwork, dsmall, comp = sc.get("dfl_work", dwb), sc.get("dfl_out", dob), sc.get("dfl_comp", ccap)
             if self.timing:
                 ctx.event_record(0)
             ctx.fmt_rows(a, work.ptr, work.nbytes, out.ptr, text.ptr, text.nbytes)
             if self.timing:
                 ctx.event_record(1)
+            if self.bgzf:
+                ctx.bgzf_deflate(text.ptr, text.nbytes, out.ptr + 64, len(segs), out.ptr, dwork.ptr, dwork.nbytes,
+                                 dsmall.ptr, comp.ptr, comp.nbytes)
+                if self.timing:
+                    ctx.event_record(2)
             small = out.download(np.uint8, ob)  # (synchronises: the text is complete)
             if self.timing:
                 _FORMAT_MS["calls"] += 1
@@ -916,12 +957,51 @@ class _DeviceFormatter:
             _FORMAT_MS["retries"] += 1
         if status != D.FMT_OK:
             return None, int(h["declined_pos"])
+        if n:
+            self.per_pos = max(self.per_pos, total / n)
+        if self.bgzf:
+            return self._blocks(text, out, len(segs), dwork, dsmall, comp, dob, total)
         t0 = time.perf_counter()
         body = text.download(np.uint8, total)
         _FORMAT_MS["download_ms"] += (time.perf_counter() - t0) * 1e3
         _FORMAT_MS["text_bytes"] += total
-        if n:
-            self.per_pos = max(self.per_pos, total / n)
+        return body, small[64:].view(np.int64)
+
+    def _blocks(self, text, out, n_seg, dwork, dsmall, comp, dob, text_total):
+        """(compressed bytes as uint8, span_coff) of the deflate enqueued behind the formatter; a
+        compressed buffer that was too small is repeated once, alone, at the exact total."""
+        import time
+
+        ctx = self.ctx
+        for attempt in (0, 1):
+            small = dsmall.download(np.uint8, dob)
+            if self.timing:
+                _BGZF_MS["device_ms"] += ctx.event_elapsed_ms(1, 2)
+            h = small[:64].view(D.DFL_HEADER_DTYPE)[0]
+            status, total = int(h["status"]), int(h["total_bytes"])
+            if status != D.DFL_TOO_SMALL or attempt:
+                break
+            _BGZF_MS["retries"] += 1
+            comp = self.scratch.get("dfl_comp", total)
+            if self.timing:
+                ctx.event_record(1)
+            ctx.bgzf_deflate(text.ptr, text.nbytes, out.ptr + 64, n_seg, None, dwork.ptr, dwork.nbytes, dsmall.ptr,
+                             comp.ptr, comp.nbytes)
+            if self.timing:
+                ctx.event_record(2)
+        if status != D.DFL_OK:
+            raise RuntimeError("bc_bgzf_deflate behind an accepted bc_fmt_rows: " + D.DFL_STATUS[status])
+        t0 = time.perf_counter()
+        body = comp.download(np.uint8, total)
+        _BGZF_MS["download_ms"] += (time.perf_counter() - t0) * 1e3
+        _BGZF_MS["calls"] += 1
+        _BGZF_MS["text_bytes"] += text_total
+        _BGZF_MS["comp_bytes"] += total
+        _BGZF_MS["blocks"] += int(h["n_blocks"])
+        _BGZF_MS["stored"] += int(h["n_stored"])
+        if text_total:  # from the first call on the largest ratio seen, never below a quarter
+            self.seen = max(self.seen, total / text_total, 0.25)
+            self.ratio = self.seen
         return body, small[64:].view(np.int64)
 
     def reference(self, hist, outs, L):
@@ -1073,6 +1153,7 @@ def get_basecounts(bam, references=None, min_base_quality=0, min_mapping_quality
     PLAN["decode"] = {"device": 0, "host": 0, "repaired": 0}  # fills decoded on the device / declined to the host
     PLAN.pop("select", None)  # BASECOUNT_DEVICE_SELECT: batches selected on the device / on the host (set by the run)
     PLAN.pop("format", None)  # _mode="text": references formatted on the device / on the host (set by the run)
+    PLAN.pop("bgzf", None)  # BASECOUNT_BGZF: references compressed on the device / by the host twin (set by the run)
     dp = None
     if _mode == "text":  # rows all the way, printed at the end of the call
         _mode, dp = "rows", int(_dp)
@@ -1197,6 +1278,8 @@ def _get_basecounts(bam, references, min_base_quality, min_mapping_quality, chun
         PLAN["groups"], PLAN["single"], PLAN["ops"] = [], [], []
         if dp is not None:
             PLAN["format"] = {"device": 0, "host": 0, "declined": []}
+            if device_bgzf_on():
+                PLAN["bgzf"] = {"device": 0, "host": 0}
             if ctx is not None and _group is None and _mode == "rows" and D.fmt_supported(dp, ref_order):
                 fm = scratch.formatter = _DeviceFormatter(ctx, scratch, k, dp, long_format)
 
@@ -1481,8 +1564,11 @@ def _get_basecounts(bam, references, min_base_quality, min_mapping_quality, chun
             if dp is not None:
                 r = results[ref]
                 PLAN["format"]["host" if isinstance(r, RefData) else "device"] += 1
+                if "bgzf" in PLAN:
+                    PLAN["bgzf"]["host" if isinstance(r, RefData) else "device"] += 1
                 if isinstance(r, RefData):  # not covered, declined or empty: the host formatter
-                    r = fmt.rows_text(ref, r.counts[:k], r.pc, r.ent, r.sec, dp, long_format)
+                    r = bgzf_text(fmt.rows_text(ref, r.counts[:k], r.pc, r.ent, r.sec, dp, long_format),
+                                  k if long_format else 1)
                 out[ref] = {"text": r, "num_reads": n}
             elif _mode == "rows":
                 out[ref] = {"rows": Rows(ref, results[ref], long_format), "num_reads": n}
@@ -1934,6 +2020,13 @@ def _timing_report(wall_s: float) -> None:
         print(f"basecount[{rank}] device format: {t['calls']} calls ({t['retries']} repeated at the exact size), "
               f"k_fmt_measure + k_fmt_scan + k_fmt_write {t['device_ms']:.3f} ms, text download {t['download_ms']:.2f} ms "
               f"for {t['text_bytes']} bytes", file=sys.stderr)
+    if _BGZF_MS["calls"]:  # BASECOUNT_BGZF=1: behind the formatter, inside the same phase
+        t = _BGZF_MS
+        print(f"basecount[{rank}] device deflate: {t['calls']} calls ({t['retries']} repeated at the exact size), "
+              f"k_dfl_plan + k_dfl_block + k_dfl_scan + k_dfl_pack {t['device_ms']:.3f} ms, {t['blocks']} blocks "
+              f"({t['stored']} stored), {t['comp_bytes']} bytes for {t['text_bytes']} of text "
+              f"(ratio {t['comp_bytes'] / max(1, t['text_bytes']):.3f}), download {t['download_ms']:.2f} ms",
+              file=sys.stderr)
     print(f"basecount[{rank}] wall {wall_s * 1e3:.2f} ms", file=sys.stderr)
 
 
@@ -1947,7 +2040,16 @@ def _run(args, references, min_base_quality, min_mapping_quality, chunk_size, be
         if group is None and device_format_on():
             # the rows as text, written on the device where bc_fmt_rows covers them
             out = get_basecounts(args.bam, **kw, _mode="text", _dp=dp)
-            print("\t".join(_columns(args.show_n_bases, args.long_format)))
+            head = "\t".join(_columns(args.show_n_bases, args.long_format))
+            if device_bgzf_on():  # the column line a block of its own, every reference a run of whole blocks
+                from . import bgzf
+
+                with _phase("format + write"), bgzf.Writer() as w:
+                    w.write((head + "\n").encode())
+                    for ref in out:
+                        w.write_blocks(out[ref]["text"])
+                return
+            print(head)
             with _phase("format + write"):
                 for ref in out:
                     fmt.write_bytes(out[ref]["text"])
@@ -1963,15 +2065,25 @@ def _run(args, references, min_base_quality, min_mapping_quality, chunk_size, be
                                                   rows.long))
             return
         out, owner, order = get_basecounts(args.bam, **kw, _group=group)
+        head = "\t".join(_columns(args.show_n_bases, args.long_format))
         if group.rank == 0:
-            print("\t".join(_columns(args.show_n_bases, args.long_format)), flush=True)
+            if device_bgzf_on():
+                fmt.write_bytes(bgzf_text((head + "\n").encode()))
+            else:
+                print(head, flush=True)
         group.barrier()
         blocks = {}
         for ref, v in out.items():
             rows = v["rows"]
             d = rows.d
-            blocks[ref] = fmt.rows_text(ref, d.counts[: rows.k], d.pc, d.ent, d.sec, dp, rows.long)
+            # (a sharded run under BASECOUNT_BGZF: every rank compresses its own rows with the host twin)
+            blocks[ref] = bgzf_text(fmt.rows_text(ref, d.counts[: rows.k], d.pc, d.ent, d.sec, dp, rows.long),
+                                    rows.k if rows.long else 1)
         dist.ordered_write(group, order, owner, blocks, write=fmt.write_bytes)
+        if device_bgzf_on() and group.rank == 0:  # (ordered_write ends on a barrier: every rank has written)
+            from . import bgzf
+
+            fmt.write_bytes(bgzf.EOF)
         return
 
     bed_errors = {}

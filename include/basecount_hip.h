@@ -850,6 +850,52 @@ int bc_fmt_rows_bytes(int64_t n, int64_t n_seg, size_t* work_bytes, size_t* out_
 int bc_fmt_rows(bc_ctx* ctx, const bc_fmt_args* args, void* d_work, size_t work_bytes, void* d_out, uint8_t* d_text,
                 int64_t text_cap);
 
+/* ---- BGZF deflate on the device (bc_deflate.hip over bc_deflate.h) -------------------------------
+ * Spans of text into whole BGZF blocks: span i is the bytes [span_off[i], span_off[i + 1]) of the
+ * text and becomes ceil(bytes / 65280) blocks of 65,280 input bytes (the last one shorter; an empty
+ * span becomes none), each one DEFLATE block with the fixed Huffman codes, or a stored block where
+ * those would take at least len + 5 bytes.  The compressed bytes are a pure function of the text
+ * and the cut: bc_bgzf_deflate_host writes the same bytes.  No EOF block is appended.
+ * d_out_small receives a 64-byte bc_dfl_header followed by span_coff[n_spans + 1] (int64): span i's
+ * blocks are the bytes [span_coff[i], span_coff[i + 1]) of d_comp.
+ * Declined, never failed (the device call returns BC_OK in every case below).  BC_DFL_TOO_SMALL:
+ * total_bytes > comp_cap; total_bytes and span_coff are exact, nothing was written to d_comp, and
+ * the call can be repeated with a buffer of that size.  BC_DFL_GATED: *d_gate != 0 (d_gate may be
+ * NULL): every kernel returned at once and nothing but the header was written.  Pointing d_span_off
+ * at bc_fmt_rows' seg_off and d_gate at its header's status puts the call behind the formatter with
+ * no host round trip.  BC_DFL_OFFSETS: the offsets decrease, are negative or pass text_cap.
+ * Whatever the offsets hold, nothing is read outside the text's aligned 32-bit words, nothing is
+ * written at or past min(total_bytes, comp_cap).                                                  */
+#define BC_DFL_OK 0
+#define BC_DFL_TOO_SMALL 1
+#define BC_DFL_GATED 2
+#define BC_DFL_OFFSETS 3
+
+typedef struct bc_dfl_header {
+    int32_t status;      /* BC_DFL_* */
+    int32_t n_stored;    /* blocks written by the stored fallback */
+    int64_t n_blocks;
+    int64_t total_bytes; /* compressed */
+    int64_t text_bytes;  /* span_off[n_spans] - span_off[0] */
+    int64_t reserved[4];
+} bc_dfl_header;
+
+/* Host arithmetic: the bytes of d_work (a 64 KiB slot per possible block: text_cap / 65280 + n_spans
+ * of them) and of d_out_small, monotone in both arguments.                                         */
+int bc_bgzf_deflate_bytes(int64_t text_cap, int64_t n_spans, size_t* work_bytes, size_t* out_small_bytes);
+/* Stream-ordered, no allocation, no synchronisation: capturable.  Launch sizes depend on text_cap and
+ * n_spans only.  d_work: 16-byte aligned; d_span_off and d_out_small: 8-byte aligned.  BC_E_ARG
+ * before any device is touched: NULL pointer (d_gate excepted), negative sizes, n_spans < 1,
+ * text_cap >= 2^40, a misaligned buffer, a work buffer smaller than bc_bgzf_deflate_bytes.          */
+int bc_bgzf_deflate(bc_ctx* ctx, const uint8_t* d_text, int64_t text_cap,
+                    const int64_t* d_span_off /* [n_spans + 1], device, any byte alignment of the values */,
+                    int64_t n_spans, const int32_t* d_gate /* may be NULL */, void* d_work, size_t work_bytes,
+                    void* d_out_small, uint8_t* d_comp, int64_t comp_cap);
+/* The twin over host threads (at most nthreads, capped at 16); touches no device.  Returns a
+ * BC_DFL_* status (>= 0) or BC_E_ARG; span_coff and *total are exact under BC_DFL_TOO_SMALL.       */
+int bc_bgzf_deflate_host(const uint8_t* h_text, const int64_t* h_span_off, int64_t n_spans, uint8_t* h_comp,
+                         int64_t comp_cap, int64_t* span_coff /* [n_spans + 1] */, int64_t* total, int nthreads);
+
 /* ---- Multi-GPU: one process per GPU, RCCL over xGMI---------------------------
  * Counting needs no exchange: references are independent, so each rank owns whole references
  * and runs the single-GPU path on them.  What crosses GPUs is small: the per-reference results
